@@ -20,9 +20,17 @@ error unless ``MIVOD_BENCH_SHARE_GPUS=1`` (test rehearsal: ranks share GPUs
 over ``MIVOD_TRANSPORT=gloo-gpu``, since RCCL refuses two ranks on one GPU).
 
 Data: synthetic, generated on the GPU once (uniform images, random labels);
-weights: random init.  Rank 0 prints ONE JSON line, with a ``comm`` record:
-gradient buckets, bytes per step, collectives per step, the exposed
-communication time (comm-stream work still running after backward's last
+weights: random init; both seeded, so the same arguments give the same inputs
+on every run.  Rank 0 prints ONE JSON line.  A plain run does only what that
+line's headline figure needs: set up, warm up, time ``--steps`` steps.
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the last timed
+step computed as float32 ``DIR/<name>.npy``: ``loss``, ``logits`` (the model's
+output for the batch) and ``params_sample`` (the updated parameters, a fixed
+seeded sample of each) — two builds can be compared output for output.
+
+``--full`` adds the ``comm`` record to the JSON line: gradient buckets, bytes
+per step, collectives per step, the exposed communication time (comm-stream work still running after backward's last
 kernel was enqueued, per step), the MEASURED allreduce time per step with
 per-bucket algorithm / bus bandwidth (timing events around every bucket
 collective on the comm stream), and what RCCL itself sees (run-time and header
@@ -89,6 +97,12 @@ def parse():
     ap.add_argument("--graph", action="store_true",
                     help="capture the whole step (fwd+bwd+allreduce+fused update) in a HIP graph "
                          "after the warmup steps and replay it (mivod.torch.make_graphed_step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, logits and a seeded sample of the "
+                         "updated parameters as float32 DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report the comm record (exposed communication time, "
+                         "per-bucket allreduce time and bandwidth, what RCCL reports)")
     return ap.parse_args()
 
 
@@ -119,9 +133,39 @@ def self_launch(argv, nproc: int, script: str = None) -> int:
     return launch(slots, cmd, extra, tag_output=False)
 
 
+DUMP_PARAM_SAMPLE = 32768        # elements kept of each parameter by --dump-outputs
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path: str, loss, logits, params) -> dict:
+    """Write the last timed step's results as float32 ``path/<name>.npy``; of every
+    parameter larger than DUMP_PARAM_SAMPLE elements a fixed, seeded sample is kept
+    (same indices on every run), so the files stay far below 64 MB in all."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.RandomState(DUMP_SEED)
+    parts = []
+    for p in params:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            idx = np.sort(rng.choice(flat.numel(), DUMP_PARAM_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        parts.append(flat.float().cpu().numpy())
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu().numpy(),
+        "logits": logits.detach().float().cpu().numpy(),
+        "params_sample": np.concatenate(parts),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return arrays
+
+
 def make_record(args, size: int, ips: float, ms: float, transport: str, comm: dict) -> dict:
-    """The ONE JSON line rank 0 prints (driver contract + BASELINE.json metric)."""
-    return {
+    """The ONE JSON line rank 0 prints (driver contract + BASELINE.json metric);
+    ``comm`` is None in a run without ``--full`` and then left out."""
+    rec = {
         "metric": BASELINE_METRIC,
         "value": round(ips, 2),
         "unit": "images/sec",
@@ -146,8 +190,10 @@ def make_record(args, size: int, ips: float, ms: float, transport: str, comm: di
             "transport": transport,
             "hip_graph": bool(args.graph),
         },
-        "comm": comm,
     }
+    if comm is not None:
+        rec["comm"] = comm
+    return rec
 
 
 def _launched() -> bool:
@@ -202,8 +248,11 @@ def main():
     images = images.to(torch.bfloat16).contiguous(memory_format=mf)
     labels = torch.randint(0, 1000, (args.batch,), device=dev, generator=g)
 
+    last = {}                         # the latest step's logits (--dump-outputs)
+
     def step():
         out = model(images)
+        last["logits"] = out.detach()
         loss = F.cross_entropy(out.float(), labels)
         loss.backward()
         opt.step()
@@ -234,6 +283,7 @@ def main():
 
     def timed_step():
         out = model(images)
+        last["logits"] = out.detach()
         loss = F.cross_entropy(out.float(), labels)
         loss.backward()
         e0 = torch.cuda.Event(enable_timing=True)
@@ -245,11 +295,12 @@ def main():
         timing.append((e0, e1))
         return loss
 
-    run = step if args.graph else timed_step
-    timed_comm = not args.graph and getattr(opt, "_mvd_comm", False)
+    # --full: timing events per step (exposed comm) and around every bucket collective
+    run = timed_step if args.full and not args.graph else step
+    timed_comm = args.full and not args.graph and getattr(opt, "_mvd_comm", False)
     if timed_comm:
         opt.time_comm(True)          # timing events around every bucket collective
-    stats0 = C.gpu_stats()
+    stats0 = C.gpu_stats() if args.full else {}
     C.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -259,25 +310,31 @@ def main():
     C.barrier()
     elapsed = time.perf_counter() - t0
     elapsed = C.max_over_ranks(elapsed)
-    stats1 = C.gpu_stats()
     ms = elapsed / max(args.steps, 1) * 1000.0
     ips = args.batch * size * args.steps / elapsed
-    plan = opt.bucket_plan()
-    grad_bytes = sum(nb for _, nb, _ in plan)
-    exposed = [max(0.0, a.elapsed_time(b)) for a, b in timing] if timing else []
-    calls = (stats1.get("calls", 0) - stats0.get("calls", 0)) / max(args.steps, 1)
-    measured = BU.comm_timing_record(opt.comm_timings() if timed_comm else [], args.steps, size)
-    comm = {
-        "buckets": len(plan),
-        "grad_bytes_per_step": grad_bytes,
-        "ring_wire_bytes_per_rank_per_step": int(2 * (size - 1) / size * grad_bytes),
-        "collectives_per_step": round(calls, 2),
-        "exposed_comm_ms": round(sum(exposed) / len(exposed), 3) if exposed else None,
-        "exposed_comm_ms_max": round(max(exposed), 3) if exposed else None,
-        **measured,
-        "rccl": BU.rccl_info(),
-    }
-    BU.check_rccl_world(comm["rccl"], size)
+    rccl = BU.rccl_info()
+    BU.check_rccl_world(rccl, size)
+    comm = None
+    if args.full:
+        stats1 = C.gpu_stats()
+        plan = opt.bucket_plan()
+        grad_bytes = sum(nb for _, nb, _ in plan)
+        exposed = [max(0.0, a.elapsed_time(b)) for a, b in timing] if timing else []
+        calls = (stats1.get("calls", 0) - stats0.get("calls", 0)) / max(args.steps, 1)
+        measured = BU.comm_timing_record(opt.comm_timings() if timed_comm else [], args.steps,
+                                         size)
+        comm = {
+            "buckets": len(plan),
+            "grad_bytes_per_step": grad_bytes,
+            "ring_wire_bytes_per_rank_per_step": int(2 * (size - 1) / size * grad_bytes),
+            "collectives_per_step": round(calls, 2),
+            "exposed_comm_ms": round(sum(exposed) / len(exposed), 3) if exposed else None,
+            "exposed_comm_ms_max": round(max(exposed), 3) if exposed else None,
+            **measured,
+            "rccl": rccl,
+        }
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, last["logits"], model.parameters())
     if rank == 0:
         print(f"[bench] warmup {args.warmup} steps {warm_s:.1f}s; loss {float(loss.detach()):.4f}; "
               f"{ms:.2f} ms/step; buckets={len(opt.bucket_plan())}; peak HBM "

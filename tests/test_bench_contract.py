@@ -73,6 +73,51 @@ def test_bench_record_schema():
     assert c["per_bucket"][0]["busbw_GBps"] > 0
 
 
+def test_bench_plain_record_and_options(monkeypatch):
+    """A plain run's line keeps the headline keys and has no comm record; the comm
+    record is behind --full, the outputs behind --dump-outputs DIR."""
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    rec = json.loads(json.dumps(bench.make_record(args, 1, 19000.0, 107.8, "local", None)))
+    assert "comm" not in rec
+    assert rec["metric"] == bench.BASELINE_METRIC and rec["value"] == 19000.0
+    assert rec["unit"] == "images/sec" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "bf16" and rec["ms_per_step"] == 107.8 and rec["steps"] == 7
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "some/dir"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "some/dir"
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: float32 .npy files; a parameter above the sample size is cut to
+    the same seeded sample on every call, a smaller one is kept whole."""
+    import numpy as np
+    import torch
+    bench = importlib.import_module("bench")
+    n = bench.DUMP_PARAM_SAMPLE
+    big = torch.arange(3 * n + 5, dtype=torch.float32).reshape(-1, 1)
+    small = torch.tensor([1.5, -2.0, 0.25], dtype=torch.bfloat16)
+    loss = torch.tensor(6.9077)
+    logits = torch.arange(12, dtype=torch.bfloat16).reshape(3, 4)
+    got = []
+    for sub in ("a", "b"):
+        d = tmp_path / sub
+        bench.dump_outputs(str(d), loss, logits, [big, small])
+        assert sorted(os.listdir(d)) == ["logits.npy", "loss.npy", "params_sample.npy"]
+        got.append({f: np.load(d / f) for f in os.listdir(d)})
+        assert all(a.dtype == np.float32 for a in got[-1].values())
+    a, b = got
+    assert a["loss.npy"].shape == (1,) and abs(float(a["loss.npy"][0]) - 6.9077) < 1e-6
+    assert np.array_equal(a["logits.npy"], np.arange(12, dtype=np.float32).reshape(3, 4))
+    ps = a["params_sample.npy"]
+    assert ps.shape == (n + 3,) and np.array_equal(ps, b["params_sample.npy"])
+    # the sample holds distinct elements of the big parameter, in index order
+    assert np.all(np.diff(ps[:n]) > 0) and ps[n - 1] <= 3 * n + 4
+    assert np.array_equal(ps[n:], np.array([1.5, -2.0, 0.25], dtype=np.float32))
+
+
 def test_rccl_info_reports_versions():
     """The comm module reports the run-time RCCL version (ncclGetVersion) next to
     the header it was compiled against, and flags a major.minor skew."""

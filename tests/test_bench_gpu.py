@@ -4,6 +4,7 @@ compression + Adasum + FusedAdamW at BASELINE.json config 5's shape (benchmarks/
 default: bs 512 x seq 128 per GPU, bf16), and the named GPU collective latency through mivod's
 RCCL communicator at world 1 with both executors.  Each asserts the run is sane (one JSON line,
 finite loss, result checked) and reports its number in the pytest terminal summary.
+`bench.py` itself is run once at a tiny shape for its `--full` / `--dump-outputs` options.
 """
 import json
 import math
@@ -40,6 +41,28 @@ def test_bench_bert_config5(cuda, mivod_report):
     mivod_report(f"BERT-Large bf16 pre-training, {cfg['global_batch']} x {cfg['seq_len']} per GPU, fp16 wire + Adasum, FusedAdamW "
                  f"(benchmarks/bench_bert.py, 6 steps): {r['value']:.1f} {r['unit']}, "
                  f"{r['ms_per_step']:.2f} ms/step, loss {r['loss']}")
+
+
+def test_bench_full_and_dump_outputs_small(cuda, tmp_path):
+    """bench.py at a tiny shape: --steps sets the timed steps, --full adds the comm record,
+    --dump-outputs writes the last step's loss / logits / parameter sample as float32."""
+    import numpy as np
+    d = tmp_path / "dump"
+    r = _run(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8",
+              "--image", "64", "--full", "--dump-outputs", str(d)], timeout=200)
+    assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert abs(r["value"] - 8 / (r["ms_per_step"] * 1e-3)) <= 0.01 * r["value"]
+    assert r["comm"]["buckets"] >= 1 and r["comm"]["grad_bytes_per_step"] > 0
+    got = {f: np.load(d / f) for f in os.listdir(d)}
+    assert sorted(got) == ["logits.npy", "loss.npy", "params_sample.npy"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["logits.npy"].shape == (8, 1000) and got["loss.npy"].shape == (1,)
+    assert sum(a.nbytes for a in got.values()) <= 64 * 2 ** 20
+    # the dumped loss is the cross entropy of the dumped logits, up to the labels: bounded by
+    # the log-sum-exp spread of the rows
+    lg = got["logits.npy"].astype(np.float64)
+    lse = np.log(np.exp(lg - lg.max(1, keepdims=True)).sum(1)) + lg.max(1)
+    assert (lse - lg.max(1)).mean() - 1e-3 <= got["loss.npy"][0] <= (lse - lg.min(1)).mean() + 1e-3
 
 
 @pytest.mark.parametrize("mode", ["native", "python"])
