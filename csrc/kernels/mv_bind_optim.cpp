@@ -1,0 +1,264 @@
+// mivod._mvk bindings: multi-tensor pack / cast, fused optimizer steps, Adasum (mv_kernels.h)
+#include "mv_checks.h"
+#include "mv_kernels.h"
+
+namespace {
+using namespace mvc;
+
+constexpr int64_t kChunk = 4096;
+
+// optional int32 device flag (non-finite result / fp16-wire overflow skip)
+int* flag_ptr(const char* fn, const char* what, const OptTensor& f, const at::Tensor& like) {
+  return vec_ptr_opt<int>(fn, what, f, like, 1, true);
+}
+
+// K1/K2: pack (to_flat) or unpack tensors <-> flat[offsets[i] : offsets[i]+numel]
+void mt_copy(const std::vector<at::Tensor>& tensors, at::Tensor flat,
+             const std::vector<int64_t>& offsets, bool to_flat, double scale,
+             c10::optional<at::Tensor> nonfinite) {
+  TORCH_CHECK(tensors.size() == offsets.size(), "mt_copy: tensors/offsets length mismatch");
+  if (tensors.empty()) return;
+  check_dense("mt_copy", "tensors", tensors[0], tensors[0], false);
+  check_dense("mt_copy", "flat", flat, tensors[0]);
+  c10::DeviceGuard guard(flat.device());
+  const int tdt = dtype_code(tensors[0]);
+  const int fdt = dtype_code(flat);
+  const int64_t fnumel = flat.numel();
+  int* nf = flag_ptr("mt_copy", "nonfinite", nonfinite, flat);
+  hipStream_t st = cur_stream();
+  MtArgs a;
+  a.ntensors = 0;
+  a.chunk_start[0] = 0;
+  auto flush = [&]() {
+    if (a.ntensors == 0) return;
+    mv_launch_mt_copy(a, tdt, flat.data_ptr(), fdt, to_flat, (float)scale, nf, st);
+    a.ntensors = 0;
+    a.chunk_start[0] = 0;
+  };
+  for (size_t i = 0; i < tensors.size(); ++i) {
+    const at::Tensor& t = tensors[i];
+    check_dense("mt_copy", "tensors", t, flat, false);
+    TORCH_CHECK(dtype_code(t) == tdt, "mt_copy: mixed tensor dtypes in one call");
+    const int64_t n = t.numel();
+    TORCH_CHECK(offsets[i] >= 0 && offsets[i] + n <= fnumel, "mt_copy: tensor ", i,
+                " [", offsets[i], ", +", n, ") exceeds flat buffer of ", fnumel);
+    if (n == 0) continue;
+    const int64_t chunks = (n + kChunk - 1) / kChunk;
+    TORCH_CHECK(chunks < (1 << 30), "mt_copy: tensor too large");
+    if (a.ntensors == kMvMaxTensors ||
+        (int64_t)a.chunk_start[a.ntensors] + chunks > (int64_t)(1u << 30))
+      flush();
+    const int k = a.ntensors++;
+    a.ptr[k] = t.data_ptr();
+    a.numel[k] = n;
+    a.flat_off[k] = offsets[i];
+    a.chunk_start[k + 1] = a.chunk_start[k] + (int32_t)chunks;
+  }
+  flush();
+}
+
+void flat_cast(at::Tensor src, at::Tensor dst, double scale, c10::optional<at::Tensor> nonfinite) {
+  check_dense("flat_cast", "src", src, src);
+  check_dense("flat_cast", "dst", dst, src);
+  TORCH_CHECK(src.numel() == dst.numel(), "flat_cast: numel mismatch");
+  c10::DeviceGuard guard(src.device());
+  mv_launch_flat_cast(src.data_ptr(), dtype_code(src), dst.data_ptr(), dtype_code(dst), src.numel(),
+                      (float)scale, flag_ptr("flat_cast", "nonfinite", nonfinite, src),
+                      cur_stream());
+}
+
+void nonfinite_scan(at::Tensor x, at::Tensor flag) {
+  check_dense("nonfinite_scan", "x", x, x);
+  int* fp = vec_ptr<int>("nonfinite_scan", "flag", flag, x, 1, true);
+  c10::DeviceGuard guard(x.device());
+  mv_launch_nonfinite_scan(x.data_ptr(), dtype_code(x), x.numel(), fp, cur_stream());
+}
+
+// The operands every fused step shares: the flat gradient, the fp32 master weights, the
+// optional low-precision model copy, the device hyperparameter block [lr, first, bc1, bc2]
+// (HIP-graph replays) and the skip flag.
+struct StepArgs {
+  float* w;
+  void* model = nullptr;
+  int model_dt = 0;
+  const float* dyn;
+  const int* skip;
+};
+
+StepArgs step_args(const char* fn, const at::Tensor& g, const at::Tensor& w, const OptTensor& model,
+                   const OptTensor& dyn, const OptTensor& skip) {
+  check_dense(fn, "grad", g, g);
+  StepArgs s;
+  s.w = vec_ptr(fn, "master", w, g, g.numel());
+  if (given(model)) {
+    check_dense(fn, "model", *model, g);
+    TORCH_CHECK(model->numel() == g.numel(), fn, ": model numel mismatch");
+    s.model = model->data_ptr();
+    s.model_dt = dtype_code(*model);
+  }
+  s.dyn = vec_ptr_opt(fn, "dyn", dyn, g, 4, true);
+  s.skip = flag_ptr(fn, "skip", skip, g);
+  return s;
+}
+
+void sgd_step(at::Tensor g, at::Tensor w, c10::optional<at::Tensor> mom,
+              c10::optional<at::Tensor> model, double lr, double momentum, double dampening,
+              double wd, double gscale, bool nesterov, bool first, c10::optional<at::Tensor> dyn,
+              c10::optional<at::Tensor> skip) {
+  const StepArgs s = step_args("sgd_step", g, w, model, dyn, skip);
+  float* mp = vec_ptr_opt("sgd_step", "momentum", mom, g, g.numel());
+  c10::DeviceGuard guard(g.device());
+  mv_launch_sgd(g.data_ptr(), dtype_code(g), s.w, mp, s.model, s.model_dt, g.numel(), (float)lr,
+                (float)momentum, (float)dampening, (float)wd, (float)gscale, nesterov, first,
+                s.dyn, s.skip, cur_stream());
+}
+
+void adam_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
+               c10::optional<at::Tensor> model, double lr, double b1, double b2, double eps,
+               double wd, double gscale, int64_t step, bool adamw, bool keras_eps,
+               c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
+  const StepArgs s = step_args("adam_step", g, w, model, dyn, skip);
+  float* mp = vec_ptr("adam_step", "exp_avg", m, g, g.numel());
+  float* vp = vec_ptr("adam_step", "exp_avg_sq", v, g, g.numel());
+  TORCH_CHECK(step >= 1, "adam_step: step must be >= 1");
+  const double bc1 = 1.0 - std::pow(b1, (double)step);
+  const double bc2 = 1.0 - std::pow(b2, (double)step);
+  c10::DeviceGuard guard(g.device());
+  mv_launch_adam(g.data_ptr(), dtype_code(g), s.w, mp, vp, s.model, s.model_dt, g.numel(),
+                 (float)lr, (float)b1, (float)b2, (float)eps, (float)wd, (float)gscale, (float)bc1,
+                 (float)bc2, adamw, keras_eps, s.dyn, s.skip, cur_stream());
+}
+
+void adadelta_step(at::Tensor g, at::Tensor w, at::Tensor sq, at::Tensor acc,
+                   c10::optional<at::Tensor> model, double lr, double rho, double eps, double wd,
+                   double gscale, c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
+  const StepArgs s = step_args("adadelta_step", g, w, model, dyn, skip);
+  float* sp = vec_ptr("adadelta_step", "square_avg", sq, g, g.numel());
+  float* ap = vec_ptr("adadelta_step", "acc_delta", acc, g, g.numel());
+  c10::DeviceGuard guard(g.device());
+  mv_launch_adadelta(g.data_ptr(), dtype_code(g), s.w, sp, ap, s.model, s.model_dt, g.numel(),
+                     (float)lr, (float)rho, (float)eps, (float)wd, (float)gscale, s.dyn, s.skip,
+                     cur_stream());
+}
+
+// the chunk -> segment tables of the segmented kernels, on `like`'s device
+ChunkTable make_table(const char* fn, const at::Tensor& like, const at::Tensor& begin,
+                      const at::Tensor& len, const at::Tensor& seg, const at::Tensor& seg_c0,
+                      const at::Tensor& seg_nc) {
+  ChunkTable ct;
+  ct.nchunks = (int32_t)begin.numel();
+  ct.nseg = (int32_t)seg_c0.numel();
+  ct.begin = vec_ptr<int64_t>(fn, "chunk begin", begin, like, ct.nchunks);
+  ct.len = vec_ptr<int32_t>(fn, "chunk len", len, like, ct.nchunks);
+  ct.seg = vec_ptr<int32_t>(fn, "chunk seg", seg, like, ct.nchunks);
+  ct.seg_c0 = vec_ptr<int32_t>(fn, "seg_c0", seg_c0, like, ct.nseg);
+  ct.seg_nc = vec_ptr<int32_t>(fn, "seg_nc", seg_nc, like, ct.nseg);
+  return ct;
+}
+
+void lars_step(at::Tensor g, at::Tensor w, at::Tensor mom, c10::optional<at::Tensor> model,
+               at::Tensor cbeg, at::Tensor clen, at::Tensor cseg, at::Tensor seg_c0,
+               at::Tensor seg_nc, at::Tensor sflag, at::Tensor partial, at::Tensor norms, double lr,
+               double momentum, double wd, double eta, double gscale, double eps, bool first,
+               c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
+  const StepArgs s = step_args("lars_step", g, w, model, dyn, skip);
+  float* mp = vec_ptr("lars_step", "momentum", mom, g, g.numel());
+  ChunkTable ct = make_table("lars_step", g, cbeg, clen, cseg, seg_c0, seg_nc);
+  int32_t* fp = vec_ptr<int32_t>("lars_step", "sflag", sflag, g, ct.nseg, true);
+  float* pp = vec_ptr("lars_step", "partial", partial, g, 2 * (int64_t)ct.nchunks, true);
+  float* np = vec_ptr("lars_step", "norms", norms, g, 2 * (int64_t)ct.nseg, true);
+  c10::DeviceGuard guard(g.device());
+  mv_launch_lars(g.data_ptr(), dtype_code(g), s.w, mp, s.model, s.model_dt, ct, fp, pp, np,
+                 (float)lr, (float)momentum, (float)wd, (float)eta, (float)gscale, (float)eps, first,
+                 s.dyn, s.skip, cur_stream());
+}
+
+void seg_dot3(at::Tensor a, at::Tensor b, at::Tensor cbeg, at::Tensor clen, at::Tensor cseg,
+              at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor partial, at::Tensor out,
+              bool swap) {
+  check_dense("seg_dot3", "a", a, a);
+  check_dense("seg_dot3", "b", b, a);
+  TORCH_CHECK(a.numel() == b.numel(), "seg_dot3: a/b numel mismatch");
+  TORCH_CHECK(a.scalar_type() == b.scalar_type() || a.scalar_type() == at::kFloat,
+              "seg_dot3: a must match b or be fp32");
+  ChunkTable ct = make_table("seg_dot3", a, cbeg, clen, cseg, seg_c0, seg_nc);
+  float* pp = vec_ptr("seg_dot3", "partial", partial, a, 3 * (int64_t)ct.nchunks, true);
+  float* op = vec_ptr("seg_dot3", "out", out, a, 3 * (int64_t)ct.nseg, true);
+  c10::DeviceGuard guard(a.device());
+  if (a.scalar_type() == b.scalar_type())
+    mv_launch_seg_dot3(a.data_ptr(), b.data_ptr(), dtype_code(a), ct, pp, op, swap ? 1 : 0,
+                       cur_stream());
+  else
+    mv_launch_seg_dot3_f(a.data_ptr<float>(), b.data_ptr(), dtype_code(b), ct, pp, op,
+                         swap ? 1 : 0, cur_stream());
+}
+
+void adasum_merge(at::Tensor fin, at::Tensor f, at::Tensor r, at::Tensor cbeg, at::Tensor clen,
+                  at::Tensor cseg, at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor rows,
+                  int64_t nrows, bool swap, c10::optional<at::Tensor> emit, int64_t elo,
+                  int64_t ehi) {
+  check_dense("adasum_merge", "fin", fin, fin);
+  float* fp = vec_ptr("adasum_merge", "f", f, fin, fin.numel());
+  check_dense("adasum_merge", "r", r, fin);
+  TORCH_CHECK(r.numel() == f.numel(), "adasum_merge: size mismatch");
+  TORCH_CHECK(fin.scalar_type() == at::kFloat || fin.scalar_type() == r.scalar_type(),
+              "adasum_merge: fin must be fp32 or the wire dtype");
+  ChunkTable ct = make_table("adasum_merge", fin, cbeg, clen, cseg, seg_c0, seg_nc);
+  TORCH_CHECK(nrows >= 1, "adasum_merge: nrows must be >= 1");
+  float* rp = vec_ptr("adasum_merge", "rows", rows, fin, nrows * 3 * (int64_t)ct.nseg, true);
+  void* ep = nullptr;
+  if (given(emit)) {
+    check_dense("adasum_merge", "emit", *emit, fin);
+    TORCH_CHECK(emit->scalar_type() == r.scalar_type() && emit->numel() == f.numel(),
+                "adasum_merge: emit must be a full-length wire-dtype buffer");
+    TORCH_CHECK(0 <= elo && elo <= ehi && ehi <= f.numel(), "adasum_merge: emit range");
+    ep = emit->data_ptr();
+  }
+  c10::DeviceGuard guard(f.device());
+  mv_launch_adasum_merge(fin.data_ptr(), dtype_code(fin), fp, r.data_ptr(), dtype_code(r), ct, rp,
+                         (int)nrows, (int)(rows.numel() / nrows), swap ? 1 : 0, ep, elo, ehi,
+                         cur_stream());
+}
+
+void adasum_combine(at::Tensor a, at::Tensor b, at::Tensor cbeg, at::Tensor clen, at::Tensor cseg,
+                    at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor dots) {
+  check_dense("adasum_combine", "a", a, a);
+  check_dense("adasum_combine", "b", b, a);
+  TORCH_CHECK(a.numel() == b.numel() && a.scalar_type() == b.scalar_type(),
+              "adasum_combine: a/b mismatch");
+  ChunkTable ct = make_table("adasum_combine", a, cbeg, clen, cseg, seg_c0, seg_nc);
+  float* dp = vec_ptr("adasum_combine", "dots", dots, a, 3 * (int64_t)ct.nseg, true);
+  c10::DeviceGuard guard(a.device());
+  mv_launch_adasum_combine(a.data_ptr(), b.data_ptr(), dtype_code(a), ct, dp, cur_stream());
+}
+
+void adasum_fcombine(at::Tensor f, at::Tensor r, at::Tensor cbeg, at::Tensor clen, at::Tensor cseg,
+                     at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor dots, bool swap) {
+  float* fp = vec_ptr("adasum_fcombine", "f", f, f, f.numel());
+  check_dense("adasum_fcombine", "r", r, f);
+  TORCH_CHECK(f.numel() == r.numel(), "adasum_fcombine: f/r numel mismatch");
+  ChunkTable ct = make_table("adasum_fcombine", f, cbeg, clen, cseg, seg_c0, seg_nc);
+  float* dp = vec_ptr("adasum_fcombine", "dots", dots, f, 3 * (int64_t)ct.nseg, true);
+  c10::DeviceGuard guard(f.device());
+  mv_launch_adasum_fcombine(fp, r.data_ptr(), dtype_code(r), ct, dp, swap ? 1 : 0, cur_stream());
+}
+
+}  // namespace
+
+void bind_optim(pybind11::module_& m) {
+  m.attr("CHUNK") = kChunk;
+  m.attr("MAX_TENSORS_PER_LAUNCH") = kMvMaxTensors;
+  m.def("mt_copy", &mt_copy, "multi-tensor pack/unpack with fused cast+scale");
+  m.def("flat_cast", &flat_cast, "flat cast + scale (compress/decompress)");
+  m.def("nonfinite_scan", &nonfinite_scan, "flag |= any non-finite element (read-only)");
+  m.def("sgd_step", &sgd_step, "fused flat SGD(+momentum, nesterov) step");
+  m.def("adam_step", &adam_step, "fused flat Adam/AdamW step");
+  m.def("adadelta_step", &adadelta_step, "fused flat Adadelta step");
+  m.def("lars_step", &lars_step, "fused segmented LARS step");
+  m.def("seg_dot3", &seg_dot3, "per-segment (a.b, |a|^2, |b|^2) (swap: (a.b, |b|^2, |a|^2))");
+  m.def("adasum_merge", &adasum_merge,
+        "one vector-halving Adasum level: merge with fixed-order group Gram sums + fused wire cast");
+  m.def("adasum_combine", &adasum_combine, "per-segment Adasum merge a <- ca*a + cb*b");
+  m.def("adasum_fcombine", &adasum_fcombine,
+        "vector-halving Adasum merge on the fp32 running sum f <- cf*f + cr*r");
+}
