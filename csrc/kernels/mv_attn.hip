@@ -30,31 +30,20 @@
 // covering every key, dQ written once in bf16 and delta computed in-kernel.
 // Dropout masks are regenerated from a counter hash of
 // (seed, b*h, query, key) in both passes.
-#include "mv_common.h"
+#include "mv_mfma.h"
 #include "mv_attn.h"
 
 
 namespace mv {
 namespace attn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 constexpr int D = 64;
 constexpr int KB = 64;     // keys per block
 constexpr int QB = 64;     // queries per block
 constexpr int PAD = 8;     // LDS row padding (elements): 144-B rows spread banks
 constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
 
 // Counter-based dropout decision, identical in forward and backward.  One hash per PAIR
 // of keys (2j, 2j + 1) of a query: 32 bits of mix32 (a bijection) of the (b, h) key xor
@@ -77,10 +66,6 @@ __device__ __forceinline__ bool keep_elem(uint32_t dkey, uint32_t q, uint32_t k,
   return drop_keep(drop_pair(dkey, q, k), k, thresh);
 }
 
-__device__ __forceinline__ f32x4v mfma(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ unsigned short bf16_bits(float x) {
   return __builtin_bit_cast(unsigned short, (__bf16)x);
 }
@@ -97,23 +82,10 @@ __device__ __forceinline__ bf16x8 ld_b128(const __bf16* p) {
   return *reinterpret_cast<const bf16x8*>(p);
 }
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-// gfx950 transposed LDS read (ds_read_b64_tr_b16): each 16-lane group reads a 4-row x
-// 16-column block of a row-major bf16 LDS array and lane c receives column col0 + c of
-// rows r0 .. r0 + 3 — the k-major MFMA operand straight from a row-major image, no
-// transposed copy.  Lane c supplies the address of row r0 + c/4, columns 4(c%4) ...
+// mv_mfma.h's transposed LDS read on an unswizzled row-major image of `stride` elements
+// per row: lane c receives column col0 + c of rows r0 .. r0 + 3
 __device__ __forceinline__ s16x4 tr4(const __bf16* base, int stride, int r0, int col0, int c) {
-  const __bf16* p = base + (r0 + (c >> 2)) * stride + col0 + 4 * (c & 3);
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-}
-
-// two 4-element transposed reads as one MFMA operand (a vector shuffle, so the register
-// allocator can place the halves adjacently instead of copying element by element)
-__device__ __forceinline__ bf16x8 cat8(const s16x4& a, const s16x4& b) {
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 o = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, o);
+  return lds_tr4(base + (r0 + (c >> 2)) * stride + col0 + 4 * (c & 3));
 }
 
 // 8 k-values: rows ra .. ra+3 then rb .. rb+3 of column col0 + c
@@ -121,14 +93,13 @@ __device__ __forceinline__ bf16x8 tr8(const __bf16* base, int stride, int ra, in
                                       int c) {
   const s16x4 a = tr4(base, stride, ra, col0, c);
   const s16x4 b = tr4(base, stride, rb, col0, c);
-  return cat8(a, b);
+  return cat8_shuffle(a, b);
 }
 
 // Ks image of bwd_short_kernel: 128-B rows (no padding) with the 16-B chunk of column
-// `col` stored at chunk (col / 8) ^ ks_swz(row); the transposed dQ reads (rows 8g + c/4 of
-// a 32-lane half take rows {r..r+3, r+8..r+11}) then hit 16 distinct 16-B bank windows
-// (padded rows left them 2-way; the same XOR as the 256x256 GEMM's weight-gradient image)
-__device__ __forceinline__ int ks_swz(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
+// `col` stored at chunk (col / 8) ^ ks_swz(row), mv_mfma.h's tr_swz8 (padded rows left the
+// transposed dQ reads 2-way conflicted)
+__device__ __forceinline__ int ks_swz(int row) { return tr_swz8(row); }
 __device__ __forceinline__ int ks_off(int row, int col) {
   return row * D + ((((col >> 3) ^ ks_swz(row)) << 3) | (col & 7));
 }
@@ -140,11 +111,9 @@ __device__ __forceinline__ const __bf16* ks_base(const __bf16* ks, int n, int g,
   return ks + ks_off(8 * g + (c >> 2), 16 * n + 4 * (c & 3));
 }
 __device__ __forceinline__ bf16x8 tr8_ks(const __bf16* base_n, int ks) {
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)(base_n + 32 * ks * D));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)(base_n + (32 * ks + 4) * D));
-  return cat8(a, b);
+  const s16x4 a = lds_tr4(base_n + 32 * ks * D);
+  const s16x4 b = lds_tr4(base_n + (32 * ks + 4) * D);
+  return cat8_shuffle(a, b);
 }
 
 __device__ __forceinline__ bf16x8 zero8() {
@@ -836,9 +805,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void b
           dsc[u][r] = ds;
         }
         // dS^T[key keyc][queries 16 qt + 4 g .. + 3]
-        typedef uint32_t u32x2s __attribute__((ext_vector_type(2)));
-        *reinterpret_cast<u32x2s*>(&dSt[ks_off(keyc, 16 * qt + 4 * g)]) =
-            u32x2s{cvt_pk_bf16(dsc[u][0], dsc[u][1]), cvt_pk_bf16(dsc[u][2], dsc[u][3])};
+        *reinterpret_cast<u32x2*>(&dSt[ks_off(keyc, 16 * qt + 4 * g)]) =
+            u32x2{cvt_pk_bf16(dsc[u][0], dsc[u][1]), cvt_pk_bf16(dsc[u][2], dsc[u][3])};
       }
       float zb[8] = {zc[0][0], zc[0][1], zc[0][2], zc[0][3], zc[1][0], zc[1][1], zc[1][2], zc[1][3]};
       float sb[8] = {dsc[0][0], dsc[0][1], dsc[0][2], dsc[0][3],
@@ -920,15 +888,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void b
     __bf16* dv = dk + (int64_t)p.h * D;
     // a lane's 4 consecutive d of tile n as one 8-byte store (lanes g = 0..3 of a key then
     // cover 32 contiguous bytes), not 4 two-byte stores
-    typedef uint32_t u32x2a __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
       const float k4[4] = {dKt[n][0] * qscale, dKt[n][1] * qscale, dKt[n][2] * qscale,
                            dKt[n][3] * qscale};
-      *reinterpret_cast<u32x2a*>(dk + 16 * n + 4 * g) =
-          u32x2a{cvt_pk_bf16(k4[0], k4[1]), cvt_pk_bf16(k4[2], k4[3])};
-      *reinterpret_cast<u32x2a*>(dv + 16 * n + 4 * g) =
-          u32x2a{cvt_pk_bf16(dVt[n][0], dVt[n][1]), cvt_pk_bf16(dVt[n][2], dVt[n][3])};
+      *reinterpret_cast<u32x2*>(dk + 16 * n + 4 * g) =
+          u32x2{cvt_pk_bf16(k4[0], k4[1]), cvt_pk_bf16(k4[2], k4[3])};
+      *reinterpret_cast<u32x2*>(dv + 16 * n + 4 * g) =
+          u32x2{cvt_pk_bf16(dVt[n][0], dVt[n][1]), cvt_pk_bf16(dVt[n][2], dVt[n][3])};
     }
   }
 }

@@ -28,14 +28,6 @@ namespace tx {
 
 constexpr int kRowsPerBlock = 64;      // 4 waves x 16 rows
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
 // Dropout keep bits of columns c .. c + 7 of one row (c % 8 == 0): one mix32 per column
 // PAIR (the row key + pair index, as the attention kernels' drop_pair), its low 16 bits
 // deciding the even column and its high 16 bits the odd one; drop when below

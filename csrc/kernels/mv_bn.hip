@@ -579,17 +579,6 @@ static dim3 grid_of(const Geo& g) {
 // grid the kernels whose VGPR count allows 7 (not 8) workgroups per CU ran a
 // second, 1/7-full round as a tail — the stats pass sat at ~4.6 TB/s
 // (scripts/micro_bn.py).  Each workgroup streams one contiguous row range.
-static int num_cus() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
-      v = 256;
-    return v;
-  }();
-  return n;
-}
-
 static int resident_blocks(const void* fn) {
   static std::mutex mu;
   static std::unordered_map<const void*, int> cache;
@@ -599,7 +588,7 @@ static int resident_blocks(const void* fn) {
   int per = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, kBlock, 0) != hipSuccess || per < 1)
     per = 1;
-  const int r = per * num_cus();
+  const int r = per * mv::num_cus();
   cache.emplace(fn, r);
   return r;
 }

@@ -1,5 +1,7 @@
 // mivod CDNA4 (gfx950) kernel helpers: dtype tags, 8-wide vector load/store
-// with fused conversion, wave64 reductions.
+// with fused conversion, wave64 reductions, the dropout hash, the CU count.  What only
+// the matrix-core kernels share (MFMA, LDS swizzles, transposed reads, LDS-DMA) is in
+// mv_mfma.h, which includes this header.
 //
 // Every memory-bound mivod kernel moves 8 elements per lane per step: 16 B for
 // bf16/fp16 (one global_load_dwordx4) and 32 B for fp32 (two dwordx4).  The
@@ -20,6 +22,19 @@ constexpr int kChunk = 4096;       // elements per workgroup (2 steps of 256x8)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+
+// Compute units of the current device (256 if the query fails), asked once per process:
+// the persistent kernels size their grids by it.
+inline int num_cus() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
+      v = 256;
+    return v;
+  }();
+  return n;
+}
 
 template <typename T> struct DT;
 template <> struct DT<float> { static constexpr Dtype v = F32; };
@@ -149,6 +164,17 @@ __device__ __forceinline__ float gelu_grad(float v) {
   float cdf, e;
   gelu_parts(v, &cdf, &e);
   return __builtin_fmaf(v * kInvSqrt2Pi, e, cdf);
+}
+
+// lowbias32 integer hash (a bijection of 32 bits): the dropout generators of mv_attn.hip
+// and mv_bert.hip, mirrored in Python by tests/test_dropout_stats.py
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
 }
 
 // wave64 sum via DPP-backed shuffles

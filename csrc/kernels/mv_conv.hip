@@ -21,7 +21,7 @@
 //
 // MFMA mapping as mv_gemm.hip: the filter tile is the A operand, so each lane's 4
 // accumulators are 4 consecutive output channels of one output pixel (8-byte stores).
-#include "mv_common.h"
+#include "mv_mfma.h"
 #include "mv_conv.h"
 #include "mv_gemm.h"
 
@@ -31,39 +31,9 @@
 namespace mv {
 namespace conv {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BK = 64;              // input channels per K step (one tap)
 
 __device__ __attribute__((aligned(16))) uint32_t g_zero[32];   // zero page for padding taps
-
-__device__ __forceinline__ f32x4v mfma(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int swz(int row, int ch) { return row * BK + ((ch ^ (row & 7)) << 3); }
-__device__ __forceinline__ float round_bf16(float x) { return (float)(__bf16)x; }
-
-__device__ __forceinline__ int remap(int bid, int nwg) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
-
-__device__ __forceinline__ void glds16(const void* src, __bf16* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0,
-                                   0);
-}
-
-// LDS-DMA of 16 bytes per lane from a buffer resource at a 32-bit byte offset (an
-// out-of-range offset reads zeros).  (A device helper: the builtin written directly in the
-// conv3x3_kernel template made the host pass drop its launch stubs.)
-__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rs, uint32_t off, __bf16* lds_wave_base) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(
-      rs, (__attribute__((address_space(3))) void*)lds_wave_base, 16, off, 0, 0, 0);
-}
 
 struct Geo {
   int H, W, C, Ho, Wo, K, st;
@@ -134,17 +104,6 @@ __device__ __forceinline__ void row_info(const Geo& g, const __bf16* X, int64_t 
   }
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // EPI: 0 plain, 1 + BN statistics of y (forward), 2 the BN+ReLU (mode 1) backward reduce
 // of the BN whose output was this conv's input: y is the data gradient dy of that output,
 // d = (x_bn * scale + bias > 0) ? bf16(dy) : 0 is written instead, partials (sum d,
@@ -172,7 +131,7 @@ __attribute__((amdgpu_waves_per_eu((NS == 2 && WM * WN == 8) ? 4 : 1))) void con
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform (SGPR)
   const int wm = wid / WN, wn = wid % WN;
-  const int t = remap(blockIdx.x, gridDim.x);
+  const int t = xcd_remap(blockIdx.x, gridDim.x);
   const int nt = t % ntn;
   const int64_t stream = t / ntn, nstreams = gridDim.x / ntn;
   const int n0 = nt * BN;
@@ -190,10 +149,8 @@ __attribute__((amdgpu_waves_per_eu((NS == 2 && WM * WN == 8) ? 4 : 1))) void con
     brow[i] = (uint32_t)(((int64_t)(n0 + i * (NT / 8) + (tid >> 3)) * wrow + sc * 8) * 2);
   // LDS-DMA by buffer_load ... lds over buffer resources of X and Wt (32-bit offsets); a
   // padding tap is an out-of-range offset, read as zeros (mv_gemm256.hip AMODE 3)
-  const __amdgpu_buffer_rsrc_t rsX =
-      __builtin_amdgcn_make_buffer_rsrc((void*)X, (short)0, (int)g.xbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsW =
-      __builtin_amdgcn_make_buffer_rsrc((void*)Wt, (short)0, (int)g.wbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsX = buffer_rsrc(X, g.xbytes);
+  const __amdgpu_buffer_rsrc_t rsW = buffer_rsrc(Wt, g.wbytes);
 
   auto issue = [&](const RowInfo<A_CH>& ri, int kt, int buf) {
     int tap = cpow2 ? kt >> cshift : kt / csteps;
@@ -288,10 +245,10 @@ __attribute__((amdgpu_waves_per_eu((NS == 2 && WM * WN == 8) ? 4 : 1))) void con
           bf16x8 wf[TN], af[TM];
 #pragma unroll
           for (int a = 0; a < TN; ++a)
-            wf[a] = *reinterpret_cast<const bf16x8*>(Bs + swz(wn * WTN + a * 16 + rl, ch));
+            wf[a] = *reinterpret_cast<const bf16x8*>(Bs + swz64(wn * WTN + a * 16 + rl, ch));
 #pragma unroll
           for (int b = 0; b < TM; ++b)
-            af[b] = *reinterpret_cast<const bf16x8*>(As + swz(wm * WTM + b * 16 + rl, ch));
+            af[b] = *reinterpret_cast<const bf16x8*>(As + swz64(wm * WTM + b * 16 + rl, ch));
 #pragma unroll
           for (int a = 0; a < TN; ++a)
 #pragma unroll
@@ -419,14 +376,7 @@ static int64_t streams_for(int64_t ntm, int ntn) {
       v = 1;
     return v;
   }();
-  static int cus = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
-      v = 256;
-    return v;
-  }();
-  int64_t s = (int64_t)cus * per / ntn;
+  int64_t s = (int64_t)num_cus() * per / ntn;
   s = std::max<int64_t>(1, std::min(s, ntm));
   return s;
 }
@@ -467,15 +417,7 @@ bool mv_conv_nhwc(const void* x, const void* w, void* y, int N, int H, int W, in
   // 64 -> 64 channel 3x3 stride 1 (ResNet-50 layer1): the row-patch kernel (mv_conv64.hip)
   if (mv_conv64_supported(N, H, W, C, K, ks, stride)) {
     const int64_t M = (int64_t)N * H * W;
-    int grid = partial ? (int)mv_conv3x3_partials(M, K) : 0;
-    if (!partial) {
-      int dev = 0, cus = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          cus < 1)
-        cus = 256;
-      grid = cus;
-    }
+    const int grid = partial ? (int)mv_conv3x3_partials(M, K) : mv::num_cus();
     return mv_conv64(x, w, y, N, H, W, shift, partial, grid, st, bn_x, bn_vec, in_scale,
                      in_bias);
   }
@@ -552,7 +494,6 @@ __global__ __launch_bounds__(256) void transpose_filters_kernel(const TfTensor* 
   const int ks = tt.ks, taps = ks * ks;
   const int r = b.tap / ks, s = b.tap - r * ks;
   const int ftap = (ks - 1 - r) * ks + (ks - 1 - s);   // source tap (rotated)
-  typedef __bf16 bf16x8t __attribute__((ext_vector_type(8)));
   if (b.k0 + 64 <= tt.K && b.c0 + 64 <= tt.C && (tt.C & 7) == 0 && (tt.K & 7) == 0) {
     // full tile, 16-byte rows on both sides (round 6: the 2-byte path below moved the
     // whole model's BERT-Large filters at ~0.1 TB/s, 457 us per step)
@@ -560,17 +501,17 @@ __global__ __launch_bounds__(256) void transpose_filters_kernel(const TfTensor* 
 #pragma unroll
     for (int h = 0; h < 2; ++h) {                      // read rows k, 8 channels per lane
       const int i = lr + 32 * h;
-      *reinterpret_cast<bf16x8t*>(&tile[i][l8]) = *reinterpret_cast<const bf16x8t*>(
+      *reinterpret_cast<bf16x8*>(&tile[i][l8]) = *reinterpret_cast<const bf16x8*>(
           tt.src + ((int64_t)(b.k0 + i) * taps + ftap) * tt.C + b.c0 + l8);
     }
     __syncthreads();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {                      // write rows c, 8 filters per lane
       const int i = lr + 32 * h;
-      bf16x8t v;
+      bf16x8 v;
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = tile[l8 + j][i];
-      *reinterpret_cast<bf16x8t*>(tt.dst + ((int64_t)(b.c0 + i) * taps + b.tap) * tt.K + b.k0 +
+      *reinterpret_cast<bf16x8*>(tt.dst + ((int64_t)(b.c0 + i) * taps + b.tap) * tt.K + b.k0 +
                                   l8) = v;
     }
     return;
@@ -690,48 +631,17 @@ bool mv_conv3x3_s2_dgrad(const void* dy, const void* wt, void* dx, int Nb, int H
 namespace mv {
 namespace conv {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-// [32][64] bf16 stage tiles (128-B rows) with a row-dependent 16-byte-chunk XOR: slot
-// (r, ch) holds chunk ch ^ wswz(r).  A transposed read touches 4 rows per 16-lane group
-// and rows 8 apart in the other group of its 32-lane half; rows 2 apart share a bank
-// window on 128-B rows, so {r, r+2, r+8, r+10} get chunk offsets {0, 2, 4, 6} (XOR by
-// even values keeps a 32-byte column pair together): conflict-free instead of 4-way.
-__device__ __forceinline__ int wswz(int r) { return (((r >> 1) & 1) << 1) | (((r >> 3) & 1) << 2); }
-
-// ASM: the transposed read in inline asm (as mv_gemm256.hip's tr_asm) — hipcc treats the
-// ds_read_tr builtin as aliasing every global_load_lds in flight and waits vmcnt(0) before
-// it, so the stage issued right after the barrier drains before the first read (no
-// prefetch at all); callers then retire the reads with lds_wait() ahead of their MFMAs.
+// [32][64] bf16 stage tiles (128-B rows) with mv_mfma.h's tr_swz4 chunk XOR: slot (r, ch)
+// holds chunk ch ^ tr_swz4(r), read with tr4_swz4.
+//
+// tr8: lane c of each 16-lane group gets rows ra..ra+3, rb..rb+3 of column col0 + c.
+// ASM: the inline-asm transposed read (mv_mfma.h's lds_tr4_asm, retired with lds_wait()).
 // wgrad3x3 (9 taps, MFMA-heavy) takes the asm form (2.50 -> 2.02 ms/step at ResNet-50
 // bs2048); wgrad1x1 (HBM-bound, several workgroups per CU hide the drain) keeps the
 // builtin, whose compiler-scheduled reads interleave with the MFMAs (4.50 vs 4.06 ms/step).
 template <bool ASM>
-__device__ __forceinline__ s16x4 tr4(const __bf16* base, int r0, int col0, int c) {
-  const int r = r0 + (c >> 2), e = col0 + 4 * (c & 3);
-  const __bf16* p = base + r * 64 + (((e >> 3) ^ wswz(r)) << 3) + (e & 7);
-  if constexpr (!ASM)
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  s16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1"
-               : "=v"(v)
-               : "v"((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p));
-  return v;
-}
-__device__ __forceinline__ void lds_wait() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);     // no MFMA is hoisted above the wait
-}
-// lane c of each 16-lane group: rows ra..ra+3, rb..rb+3 of column col0 + c
-template <bool ASM>
 __device__ __forceinline__ bf16x8 tr8(const __bf16* base, int ra, int rb, int col0, int c) {
-  const s16x4 a = tr4<ASM>(base, ra, col0, c);
-  const s16x4 b = tr4<ASM>(base, rb, col0, c);
-  bf16x8 o;
-  short* q = reinterpret_cast<short*>(&o);
-  q[0] = a[0]; q[1] = a[1]; q[2] = a[2]; q[3] = a[3];
-  q[4] = b[0]; q[5] = b[1]; q[6] = b[2]; q[7] = b[3];
-  return o;
+  return cat8_copy(tr4_swz4<ASM>(base, ra, col0, c), tr4_swz4<ASM>(base, rb, col0, c));
 }
 
 constexpr int WG_NT = 256;                 // 4 waves, wave w = c tile w, all 4 k tiles
@@ -748,7 +658,7 @@ __global__ __launch_bounds__(WG_NT) void wgrad3x3_kernel(const __bf16* __restric
   __shared__ __attribute__((aligned(16))) __bf16 smem[WG_NS * WG_STAGE];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int t = remap(blockIdx.x, gridDim.x);
+  const int t = xcd_remap(blockIdx.x, gridDim.x);
   const int kc = t % nkc, ms = t / nkc;
   const int cblocks = g.C / 64;
   const int k0 = (kc / cblocks) * 64, c0 = (kc % cblocks) * 64;
@@ -759,13 +669,11 @@ __global__ __launch_bounds__(WG_NT) void wgrad3x3_kernel(const __bf16* __restric
   // staging role: row tid >> 3, 16-byte chunk tid & 7 of all 10 tiles of a stage.  The
   // row's output pixel advances by 32 per stage: (n, ho, wo) is carried incrementally
   // (no per-stage division)
-  const int srow = tid >> 3, sch = (tid & 7) ^ wswz(tid >> 3);   // swizzled source chunk
+  const int srow = tid >> 3, sch = (tid & 7) ^ tr_swz4(tid >> 3);   // swizzled source chunk
   // LDS-DMA through buffer resources over X and DY (32-bit byte offsets; a padding tap or a
   // row past M is an out-of-range offset, read as zeros) — conv3x3_kernel's blds16
-  const __amdgpu_buffer_rsrc_t rsX =
-      __builtin_amdgcn_make_buffer_rsrc((void*)X, (short)0, (int)g.xbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsD =
-      __builtin_amdgcn_make_buffer_rsrc((void*)DY, (short)0, (int)g.wbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsX = buffer_rsrc(X, g.xbytes);
+  const __amdgpu_buffer_rsrc_t rsD = buffer_rsrc(DY, g.wbytes);
   int64_t pm = ch0 * WG_ROWS + srow;           // this thread's row of the next issued stage
   // (n, ho, wo) of that row, stepped by the 32 rows of a stage with adds and compares (the
   // host keeps N H W C < 2^31: 32-bit element offsets into X) — a divergent per-lane
@@ -953,14 +861,7 @@ bool mv_wgrad3x3(const void* x, const void* dy, void* dw, float* work, int N, in
   if (mv_wgrad64_supported(N, H, W, C, K, stride)) {
     // 64 -> 64 stride 1: the row-patch kernel (mv_conv64.hip), one persistent 136-KB-LDS
     // workgroup per CU (<= ms partial rows, so the workspace above is large enough)
-    static const int cus = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          n < 1)
-        n = 256;
-      return n;
-    }();
+    const int cus = mv::num_cus();
     const int grid = ms < cus ? ms : cus;
     mv_wgrad64(x, dy, work, grid, N, H, W, st, in_scale, in_bias);
     const int64_t n = (int64_t)9 * K * C;
@@ -1012,7 +913,7 @@ __attribute__((amdgpu_waves_per_eu(FK == 2 ? 2 : 1))) void wgrad1x1_kernel(
   __shared__ __attribute__((aligned(16))) __bf16 smem[NS * STAGE];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int t = remap(blockIdx.x, gridDim.x);
+  const int t = xcd_remap(blockIdx.x, gridDim.x);
   const int kc = t % nkc, ms = t / nkc;
   const int cblocks = g.C / (64 * WC);
   const int k0 = (kc / cblocks) * (64 * KS), c0 = (kc % cblocks) * (64 * WC);
@@ -1023,7 +924,7 @@ __attribute__((amdgpu_waves_per_eu(FK == 2 ? 2 : 1))) void wgrad1x1_kernel(
   // staging role: thread group h = tid >> 8 loads sub-tiles h, h + HPW, ...; within a
   // sub-tile, row l >> 3 and (swizzled) 16-byte chunk of l = tid & 255
   const int hg = HPW == 1 ? 0 : tid >> 8, l = tid & 255;
-  const int srow = l >> 3, sch = (l & 7) ^ wswz(l >> 3);
+  const int srow = l >> 3, sch = (l & 7) ^ tr_swz4(l >> 3);
   const uint64_t zaddr = (uint64_t)(g_zero + (l & 7) * 4);
   const uint32_t hw = (uint32_t)(g.Ho * g.Wo);
   auto issue = [&](int64_t chk, int slot) {

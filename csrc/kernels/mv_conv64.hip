@@ -28,18 +28,13 @@
 //        backward reduce of the BN that produced this conv's input (this conv = its data
 //        gradient), exactly mv_conv.hip's EPI 2.
 // The bf16 conversions use cvt_pk_bf16_cc (the accumulators may live in VGPRs here).
-#include "mv_common.h"
+#include "mv_mfma.h"
 #include "mv_conv.h"
 
 #include <type_traits>
 
 namespace mv {
 namespace conv64 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kC = 64;               // input = output channels
 constexpr int kR = 8;                // output rows per tile
@@ -54,16 +49,12 @@ constexpr int kFilt = kC * 9 * kC;   // filter elements
 constexpr int kPatchChunks = kPR * kPW * 8;
 constexpr int kLoads = (kPatchChunks + kThreads - 1) / kThreads;   // 16-byte loads / thread
 
-__device__ __forceinline__ f32x4v mfma(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ int fidx(int k, int tap, int c) {      // filter LDS element index
   return ((k * 9 + tap) * 8 + (c ^ (k & 7))) * 8;
 }
 __device__ __forceinline__ int pidx(int row, int col, int c) {    // patch LDS element index
   return ((row * kPW + col) * 8 + (c ^ (col & 7))) * 8;
 }
-__device__ __forceinline__ float round_bf16(float x) { return (float)(__bf16)x; }
 
 struct Geo64 {
   int N, H, W;
@@ -423,17 +414,15 @@ bool mv_conv64(const void* x, const void* w, void* y, int N, int H, int W, const
 namespace mv {
 namespace conv64 {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kWThreads = 512;
 constexpr int kDyPix = kR * 56;                   // dy pixels staged per tile (W <= 56)
 constexpr int kWLoadsDy = kDyPix * 8 / kWThreads;   // 7
 constexpr int kWLoadsX = kPR;                       // 10 (one patch row per load)
 
 // dy tile: [448 px][64 k] bf16, 128-B rows; the 16-B chunk ch of pixel p is stored at
-// ch ^ dswz(p).  A transposed read's 32-lane half touches 8 consecutive pixels, 32 B each;
+// ch ^ dy_swz(p).  A transposed read's 32-lane half touches 8 consecutive pixels, 32 B each;
 // the 64 banks span 256 B, so the 4 even (odd) pixels must sit in distinct 32-B windows.
-__device__ __forceinline__ int dswz(int p) { return ((p >> 1) & 3) << 1; }
+__device__ __forceinline__ int dy_swz(int p) { return ((p >> 1) & 3) << 1; }
 // X patch: [10 rows][58 cols] pixels at a 160-B (80-element) stride, unswizzled: 8
 // consecutive pixels land on bank offsets 40 j mod 64 = {0, 40, 16, 56, 32, 8, 48, 24}
 // dwords, one 8-dword window each, and every tap shift (dr, dc) is the constant offset
@@ -442,11 +431,7 @@ constexpr int kPS = 80;                    // patch pixel stride (elements)
 constexpr int kPC = 58;                    // patch columns (W + 2 <= 58)
 
 __device__ __forceinline__ bf16x8 tr8p(const __bf16* pa, const __bf16* pb) {
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)pa);
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)pb);
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  const s16x8 o = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, o);
+  return cat8_shuffle(lds_tr4(pa), lds_tr4(pb));
 }
 
 __global__ __launch_bounds__(kWThreads, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -504,14 +489,14 @@ void wgrad64_kernel(const __bf16* __restrict__ X, const __bf16* __restrict__ DY,
   // MFMA k index -> pixel: lane group gq holds pixels 4 gq + {0..3} (first half of its 8)
   // and 16 + 4 gq + {0..3} (second half) of the 32-pixel k step, so each 32-lane half of
   // a transposed read touches 8 consecutive pixels.  dy read addresses (k step 0; the +32
-  // pixel step keeps dswz):
+  // pixel step keeps dy_swz):
   const __bf16* ads[2][2];
 #pragma unroll
   for (int u = 0; u < 2; ++u)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int r = 4 * gq + 16 * h + (cl >> 2), e = 16 * (2 * kh + u) + 4 * (cl & 3);
-      ads[u][h] = ds + r * 64 + (((e >> 3) ^ dswz(r)) << 3) + (e & 7);
+      ads[u][h] = ds + r * 64 + (((e >> 3) ^ dy_swz(r)) << 3) + (e & 7);
     }
   const __bf16* pbase = ps + (cl >> 2) * kPS + 16 * ct + 4 * (cl & 3);
   f32x4v acc[2][9];
@@ -541,7 +526,7 @@ void wgrad64_kernel(const __bf16* __restrict__ X, const __bf16* __restrict__ DY,
 #pragma unroll
     for (int i = 0; i < kWLoadsDy; ++i) {
       const int p = spix + 64 * i;
-      *reinterpret_cast<u32x4*>(ds + p * 64 + ((sch ^ dswz(p)) << 3)) = pdy[i];
+      *reinterpret_cast<u32x4*>(ds + p * 64 + ((sch ^ dy_swz(p)) << 3)) = pdy[i];
     }
     __syncthreads();
     if (t + gridDim.x < g.tiles) gload(t + gridDim.x);

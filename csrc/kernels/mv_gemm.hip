@@ -21,7 +21,7 @@
 // chunk XOR swizzle (row r's chunk c lives at c ^ (r & 7)), one barrier per
 // 64-deep K step.  Grid: 1-D, tiles remapped so the N tiles of one row block are
 // consecutive on one XCD (they share the activation rows through that XCD's L2).
-#include "mv_common.h"
+#include "mv_mfma.h"
 #include "mv_gemm.h"
 
 #include <cstdlib>
@@ -29,28 +29,8 @@
 namespace mv {
 namespace gemm {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BK = 64;
 constexpr int KC = BK / 8;          // 16-byte chunks per staged row
-
-__device__ __forceinline__ f32x4v mfma(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int swz(int row, int ch) { return row * BK + ((ch ^ (row & 7)) << 3); }
-
-__device__ __forceinline__ float round_bf16(float x) { return (float)(__bf16)x; }
-
-// bijective XCD-aware remap of the 1-D workgroup id (8 XCDs, round-robin dispatch)
-__device__ __forceinline__ int remap(int bid, int nwg) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
 
 template <int BM, int BN, int WM, int WN, bool STATS>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(
@@ -69,7 +49,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
-  const int t = remap(blockIdx.x, gridDim.x);
+  const int t = xcd_remap(blockIdx.x, gridDim.x);
   const int mt = t / ntn, nt = t - mt * ntn;
   const int64_t m0 = (int64_t)mt * BM;
   const int n0 = nt * BN;
@@ -95,12 +75,12 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(
 #pragma unroll
     for (int i = 0; i < A_CH; ++i) {
       const int q = tid + i * NT, row = q / KC, ch = q % KC;
-      *reinterpret_cast<u32x4*>(As + swz(row, ch)) = ra[i];
+      *reinterpret_cast<u32x4*>(As + swz64(row, ch)) = ra[i];
     }
 #pragma unroll
     for (int i = 0; i < B_CH; ++i) {
       const int q = tid + i * NT, row = q / KC, ch = q % KC;
-      *reinterpret_cast<u32x4*>(Bs + swz(row, ch)) = rb[i];
+      *reinterpret_cast<u32x4*>(Bs + swz64(row, ch)) = rb[i];
     }
   };
 
@@ -124,10 +104,10 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(
       bf16x8 wf[TN], af[TM];
 #pragma unroll
       for (int a = 0; a < TN; ++a)
-        wf[a] = *reinterpret_cast<const bf16x8*>(Bs + swz(wn * WTN + a * 16 + (lane & 15), ch));
+        wf[a] = *reinterpret_cast<const bf16x8*>(Bs + swz64(wn * WTN + a * 16 + (lane & 15), ch));
 #pragma unroll
       for (int b = 0; b < TM; ++b)
-        af[b] = *reinterpret_cast<const bf16x8*>(As + swz(wm * WTM + b * 16 + (lane & 15), ch));
+        af[b] = *reinterpret_cast<const bf16x8*>(As + swz64(wm * WTM + b * 16 + (lane & 15), ch));
 #pragma unroll
       for (int a = 0; a < TN; ++a)
 #pragma unroll
@@ -378,7 +358,7 @@ __global__ __launch_bounds__((stream_nt<K, BN, EPI>())) void gemm_stream_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wn = (tid >> 6) % WN;
   const int wm = (tid >> 6) / WN;            // wave set (rows wm * WTM ..)
   const int g = lane >> 4, rl = lane & 15;
-  const int t = remap(blockIdx.x, gridDim.x);
+  const int t = xcd_remap(blockIdx.x, gridDim.x);
   const int nt = t % ntn;
   const int64_t stream = t / ntn, nstreams = gridDim.x / ntn;
   const int n0 = nt * BN;
@@ -742,17 +722,6 @@ static void launch(const __bf16* A, const __bf16* B, __bf16* C, int64_t M, int N
 }  // namespace gemm
 }  // namespace mv
 
-static int num_cus() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
-      v = 256;
-    return v;
-  }();
-  return n;
-}
-
 // streaming variant: the BN it uses for (K, N), or false for the tiled kernel
 static bool stream_cfg(int K, int N, int* bn) {
   if (K == 64 || K == 128) { *bn = N % 256 == 0 ? 256 : (N % 128 == 0 ? 128 : 64); return true; }
@@ -784,7 +753,7 @@ static int64_t streams_for(int64_t M, int N) {
   }();
   const int ntn = N / BN;
   const int64_t ntm = (M + BMV - 1) / BMV;
-  int64_t streams = (int64_t)num_cus() * per / ntn;
+  int64_t streams = (int64_t)mv::num_cus() * per / ntn;
   if (streams < 1) streams = 1;
   if (streams > ntm) streams = ntm;
   return streams;
@@ -868,7 +837,7 @@ static bool launch_fold_dx(const __bf16* a, const __bf16* b, __bf16* d, int64_t 
   }();
   const int ntn = N / BN;
   const int64_t ntm = (M + 63) / 64;
-  int64_t streams = (int64_t)num_cus() * per / ntn;
+  int64_t streams = (int64_t)mv::num_cus() * per / ntn;
   if (streams < 1) streams = 1;
   if (streams > ntm) streams = ntm;
   *P = streams * stream_wm<K, BN, EPI>();           // one statistics row per wave set

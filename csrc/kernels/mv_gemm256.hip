@@ -32,7 +32,7 @@
 // 4 accumulators are 4 consecutive channels of one output row and the per-channel
 // statistics reduce over the 16 lanes of a lane group; C leaves as 16-byte stores after
 // a v_permlane16_swap exchange between n-tile pairs.
-#include "mv_common.h"
+#include "mv_mfma.h"
 #include "mv_gemm.h"
 
 #include <cstdio>
@@ -42,24 +42,10 @@
 namespace mv {
 namespace g256 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BM = 256, BN = 256, BK = 64, NT = 512;
 constexpr int HALF = 128 * BK;            // elements per half-tile (16 KB)
 constexpr int BUF = 4 * HALF;             // one K tile: A0, A1, B0, B1
 
-__device__ __forceinline__ f32x4v mfma(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ int swz(int row, int ch) { return row * BK + ((ch ^ (row & 7)) << 3); }
-__device__ __forceinline__ float round_bf16(float x) { return (float)(__bf16)x; }
-__device__ __forceinline__ int remap(int bid, int nwg) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (bid >> 3);
-}
 // Diagnostic builds only (scripts/debug/g256_diag.hip): MV_G256_DIAG drops parts of the K
 // loop to attribute its time — 1 the vmcnt waits, 2 the LDS-DMA of every K tile but a
 // tile's first, 4 the fragment reads of every K tile but a tile's first, 8 the barriers,
@@ -72,14 +58,13 @@ __device__ __forceinline__ int remap(int bid, int nwg) {
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   if constexpr (!(MV_G256_DIAG & 1) || N == 0)     // (the drain before an epilogue stays)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+    mv::wait_vm<N>();
 }
+// (mv_mfma.h's raw barrier between two scheduling barriers: nothing moves across it)
 __device__ __forceinline__ void barrier() {
   if constexpr (MV_G256_DIAG & 8) return;
   __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  raw_barrier();
   __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -179,7 +164,7 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
   const int G = gridDim.x;
   // persistent: workgroups of one XCD take consecutive tiles (the N tiles of an M block
   // share its A rows through that XCD's L2)
-  int64_t tile = remap(blockIdx.x, G);
+  int64_t tile = xcd_remap(blockIdx.x, G);
   if (tile >= p.ntiles) return;
   // G % ntn == 0 (g256_launch): a workgroup's tiles tile, tile + G, ... share one column
   // tile, so its statistics accumulate on chip and leave as ONE partial row per wave group
@@ -281,12 +266,10 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
   // and B: one 32-bit per-lane offset (the host keeps every operand below 4 GB), no 64-bit
   // address arithmetic, and an AMODE 3 / 4 padding tap is an out-of-range offset, which
   // the buffer unit answers with zeros (no zero-page select) — profiles/r5_ab_log.md
-  const __amdgpu_buffer_rsrc_t rsA =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, (int)p.abytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsA2 = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(AMODE == 2 ? p.A2 : p.A), (short)0, (int)(AMODE == 2 ? p.a2bytes : 0u), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, (int)p.bbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsA = buffer_rsrc(p.A, p.abytes);
+  const __amdgpu_buffer_rsrc_t rsA2 =
+      buffer_rsrc(AMODE == 2 ? p.A2 : p.A, AMODE == 2 ? p.a2bytes : 0u);
+  const __amdgpu_buffer_rsrc_t rsB = buffer_rsrc(p.B, p.bbytes);
   // the K tile's wave-uniform source offsets (AMODE 3: filter tap and channel block)
   struct KInfo {
     uint32_t toff, boff;
@@ -323,8 +306,7 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
     const int tap = ki.tap;
     const bool second = AMODE == 2 && kt >= KT1;      // dual source: K tiles of A2
     auto one = [&](int i) {
-      auto* dst = (__attribute__((address_space(3))) void*)(smem + buf * BUF + slot * HALF +
-                                                            (2 * w + i) * 512);
+      __bf16* dst = smem + buf * BUF + slot * HALF + (2 * w + i) * 512;
       uint32_t vo;
       if (slot >= 2) {
         vo = offb[slot - 2][i] + boff;
@@ -336,8 +318,7 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
       } else {
         vo = offa[slot][i] + (uint32_t)kt * (BK * 2);
       }
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(slot >= 2 ? rsB : (second ? rsA2 : rsA), dst, 16,
-                                               vo, 0, 0, 0);
+      blds16(slot >= 2 ? rsB : (second ? rsA2 : rsA), vo, dst);
     };
     if (ione >= 0) {
       one(ione);
@@ -365,7 +346,8 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
       if (h == 0 || b < MH1)
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
-          af[b][kk] = *reinterpret_cast<const bf16x8*>(base + swz(wm * 64 + b * 16 + rl, kk * 4 + g));
+          af[b][kk] =
+              *reinterpret_cast<const bf16x8*>(base + swz64(wm * 64 + b * 16 + rl, kk * 4 + g));
   };
   auto read_b = [&](int buf, int h) {
     if ((MV_G256_DIAG & 4) && kt != 0) return;
@@ -374,7 +356,8 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
     for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk)
-        bfr[h][a][kk] = *reinterpret_cast<const bf16x8*>(base + swz(wn * 32 + a * 16 + rl, kk * 4 + g));
+        bfr[h][a][kk] =
+            *reinterpret_cast<const bf16x8*>(base + swz64(wn * 32 + a * 16 + rl, kk * 4 + g));
   };
   auto mma = [&](int qm, int qn) {
     __builtin_amdgcn_s_setprio(1);
@@ -542,9 +525,8 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
           }
         }
         if (in && (EPI != 1 || p.C) && !(MV_G256_DIAG & 16)) {  // EPI 1, C == null: statistics only
-          typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-          u32x4v* dst = reinterpret_cast<u32x4v*>(p.C + orow * N + c0);
-          const u32x4v val{o[0], o[1], o[2], o[3]};
+          u32x4* dst = reinterpret_cast<u32x4*>(p.C + orow * N + c0);
+          const u32x4 val{o[0], o[1], o[2], o[3]};
           // plain stores: non-temporal ones (MV_G256_DIAG 64) made the GEMMs themselves
           // 3-11% faster but the consumers slower (their reads then miss the Infinity
           // Cache): whole step +0.4% with nt everywhere, level with nt only for outputs
@@ -821,25 +803,15 @@ struct WArgs {
   uint32_t xbytes;              // gathered X (TAPS 2 / 9): byte size of the image (< 4 GB - 16)
 };
 
-__device__ __forceinline__ int wf(int r) { return ((r & 3) | (((r >> 3) & 1) << 2)) << 1; }
+// the chunk XOR of the [64 px][128 ch] images: mv_mfma.h's tr_swz8 in 32-B chunk pairs
+__device__ __forceinline__ int wf(int r) { return tr_swz8(r) << 1; }
 
-// The transposed reads are inline asm: hipcc treats the ds_read_tr builtin as aliasing
-// the in-flight LDS DMA and drains vmcnt(0) before every one (the whole prefetch).  The
-// consumer waits lgkmcnt(0) itself (mma_wait), ahead of the MFMAs.
-typedef short s16x4w __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ s16x4w tr_asm(const __bf16* p) {
-  s16x4w v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1"
-               : "=v"(v)
-               : "v"((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p));
-  return v;
-}
+// The transposed reads are the inline-asm form (LDS-DMA prefetch in flight, mv_mfma.h's
+// lds_tr4_asm); the consumer retires them with lds_wait() ahead of its MFMAs.
 __device__ __forceinline__ bf16x8 trp(const __bf16* pa, const __bf16* pb) {
-  const s16x4w a = tr_asm(pa);
-  const s16x4w b = tr_asm(pb);
-  typedef short s16x8w __attribute__((ext_vector_type(8)));
-  const s16x8w o = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, o);
+  const s16x4 a = lds_tr4_asm(pa);
+  const s16x4 b = lds_tr4_asm(pb);
+  return cat8_shuffle(a, b);
 }
 
 template <int TAPS, bool PH2, bool DM = false>
@@ -849,7 +821,7 @@ __global__ __launch_bounds__(NT, 1) void wgrad256_kernel(WArgs p) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wc = w >> 2, wk = w & 3;
   // workgroups of one XCD share a pixel split (consecutive ids: same rows, other tiles)
-  const int t = remap(blockIdx.x, gridDim.x);
+  const int t = xcd_remap(blockIdx.x, gridDim.x);
   const int split = t / p.ntiles, tl = t - split * p.ntiles;
   const int c0 = (tl % p.ntc) * 256, k0 = (tl / p.ntc) * 256;
   // TAPS = 9: this tile's filter tap and its channel block in X.  TAPS = 2: a 1x1 conv at
@@ -912,11 +884,9 @@ __global__ __launch_bounds__(NT, 1) void wgrad256_kernel(WArgs p) {
   // a row past the split's end is an out-of-range offset the buffer unit reads as zeros
   // (the host keeps a split's rows below 4 GB: mv_wgrad256_supported)
   const uint32_t nrow = me > mb ? (uint32_t)(me - mb) : 0u;
-  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(GATHER ? p.X : p.X + mb * p.C), (short)0,
-      (int)(GATHER ? p.xbytes : nrow * (uint32_t)(p.C * 2)), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(dyb + mb * ldy), (short)0, (int)(nrow * (uint32_t)(ldy * 2)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsX = buffer_rsrc(
+      GATHER ? p.X : p.X + mb * p.C, GATHER ? p.xbytes : nrow * (uint32_t)(p.C * 2));
+  const __amdgpu_buffer_rsrc_t rsD = buffer_rsrc(dyb + mb * ldy, nrow * (uint32_t)(ldy * 2));
   // issue(slot, buf, kt): the wave's 2 LDS-DMA pieces of half-tile `slot` of K tile kt;
   // ione = 0 / 1: only that piece (DM)
   auto issue = [&](int slot, int buf, int kt, int ione = -1) {
@@ -949,10 +919,7 @@ __global__ __launch_bounds__(NT, 1) void wgrad256_kernel(WArgs p) {
       } else {
         vo = lrow * (uint32_t)((slot < 2 ? p.C : ldy) * 2) + (uint32_t)(choff[slot][i] * 2);
       }
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          xsrc ? rsX : rsD,
-          (__attribute__((address_space(3))) void*)(smem + buf * BUF + slot * HALF + (2 * w + i) * 512),
-          16, vo, 0, 0, 0);
+      blds16(xsrc ? rsX : rsD, vo, smem + buf * BUF + slot * HALF + (2 * w + i) * 512);
     }
   };
 
@@ -986,8 +953,7 @@ __global__ __launch_bounds__(NT, 1) void wgrad256_kernel(WArgs p) {
       }
   };
   auto mma = [&](int qc, int qk) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // this phase's asm reads
-    __builtin_amdgcn_sched_barrier(0);
+    lds_wait();                                           // this phase's asm reads
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
@@ -1000,8 +966,7 @@ __global__ __launch_bounds__(NT, 1) void wgrad256_kernel(WArgs p) {
   };
   // DM: gemm256_kernel's mma_dm (LDS-DMA piece j after MFMA 1 + j * step)
   auto mma_dm = [&](int qc0, int qk0, int qc1, int qk1, int npc, int step, auto&& piece) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // this phase's asm reads
-    __builtin_amdgcn_sched_barrier(0);
+    lds_wait();                                           // this phase's asm reads
     __builtin_amdgcn_s_setprio(1);
     int t = 0;
 #pragma unroll
@@ -1163,17 +1128,6 @@ static bool g256_opt(const char* tok) {
   return v.find(std::string(",") + tok + ",") != std::string::npos;
 }
 
-static int g256_cus() {
-  static const int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
-      v = 256;
-    return v;
-  }();
-  return n;
-}
-
 // Row-block height: 224 (MT = 7) when the blocks tile M exactly and there is one column tile
 // (N = 256: ResNet-50 layer 3's 1024 -> 256 1x1 convs, 251 -> 238 us), else 256.  A
 // cost model that picks 224 wherever it leaves fewer row-rounds for the persistent grid
@@ -1187,7 +1141,7 @@ static int g256_bm(int64_t M, int N) {
       g256_opt("bm224") ? 224 : g256_opt("bm256") ? 256 : g256_opt("bmcost") ? -1 : 0;
   if (force == 224 || force == 256) return force;
   if (force == -1) {
-    const int64_t ntn = N / mv::g256::BN, cus = g256_cus();
+    const int64_t ntn = N / mv::g256::BN, cus = mv::num_cus();
     auto cost = [&](int64_t bm) {
       const int64_t tiles = (M + bm - 1) / bm * ntn;
       int64_t g = (tiles < cus ? tiles : cus) / ntn * ntn;
@@ -1209,7 +1163,7 @@ bool mv_gemm256_supported(int64_t M, int N, int K) {
 // workgroup keeps one column tile (its statistics accumulate on chip)
 static int64_t g256_grid(int64_t M, int N) {
   const int64_t ntn = N / mv::g256::BN, bm = g256_bm(M, N);
-  const int64_t ntiles = (M + bm - 1) / bm * ntn, cus = g256_cus();
+  const int64_t ntiles = (M + bm - 1) / bm * ntn, cus = mv::num_cus();
   const int64_t g = (ntiles < cus ? ntiles : cus) / ntn * ntn;
   return g > ntn ? g : ntn;
 }
@@ -1495,7 +1449,7 @@ bool mv_dgrad256_s2(const void* dy, const void* wt, void* dx, int Nb, int H, int
 static void w256_split(int64_t M, int C, int K, int* ms, int64_t* per) {
   const int ntiles = (C / 256) * (K / 256);
   const int64_t chunks = (M + 63) / 64;
-  int m = g256_cus() / ntiles;
+  int m = mv::num_cus() / ntiles;
   if (m < 1) m = 1;
   if (m > chunks) m = (int)chunks;
   *per = (chunks + m - 1) / m;

@@ -15,16 +15,11 @@
 // Epilogue: bf16 store of 4 consecutive channels per lane + per-channel (sum, sum^2)
 // around the running mean, reduced to one [2][64] partial row per workgroup (fixed order,
 // mv_bn.hip's finalize layout).
-#include "mv_common.h"
+#include "mv_mfma.h"
 #include "mv_stem.h"
 
 namespace mv {
 namespace stem {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kH = 224, kW = 224, kC = 4, kOH = 112, kOW = 112, kCO = 64;
 constexpr int kPW = 232;                    // padded patch row (230 used: cols -3 .. 226)
@@ -38,10 +33,6 @@ constexpr int kR = MV_STEM_ROWS;
 constexpr int kIR = 2 * kR + 5;             // staged input rows
 constexpr int kPatch = kIR * kPW;           // pixels in the LDS patch
 constexpr int kLoads = (kIR * 230 + 255) / 256;   // 8-byte patch loads per thread
-
-__device__ __forceinline__ f32x4v mfma(const bf16x8& a, const bf16x8& b, const f32x4v& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 // one input pixel as the 4-channel LDS image wants it: cin = 4 (zero-padded RGB, one 8-byte
 // load) or cin = 3 (the raw RGB image, three 2-byte loads, channel 3 = 0 — no padded copy
@@ -194,15 +185,8 @@ int mv_stem_partials(int N) {
       v = 1;
     return v;
   }();
-  static int cus = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
-      v = 256;
-    return v;
-  }();
   const int64_t rows = (int64_t)N * (mv::stem::kOH / mv::stem::kR);
-  int64_t g = (int64_t)cus * per;
+  int64_t g = (int64_t)mv::num_cus() * per;
   if (g > rows) g = rows;
   return (int)g;
 }
@@ -225,33 +209,16 @@ void mv_stem_fwd(const void* x, const void* w, void* z, const float* shift, floa
 namespace mv {
 namespace stem {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int dswz(int r) { return (((r >> 1) & 1) << 1) | (((r >> 3) & 1) << 2); }
-
-// 4 pixels (rows r0 .. r0+3) of column col0 + c of the [128][64] dz tile
-__device__ __forceinline__ s16x4 dz_tr4(const __bf16* base, int r0, int col0, int c) {
-  const int r = r0 + (c >> 2), e = col0 + 4 * (c & 3);
-  const __bf16* p = base + r * 64 + (((e >> 3) ^ dswz(r)) << 3) + (e & 7);
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-}
+// The [128][64] dz tile is mv_mfma.h's tr_swz4 image: tr4_swz4<false> reads 4 pixels (rows
+// r0 .. r0+3) of column col0 + c.
 
 // 4 pixels (p0 .. p0+3, clamped to 111) of k column c of tile (r, s0) of the patch
 __device__ __forceinline__ s16x4 px_tr4(const __bf16* ps, int p0, int r, int s0, int c) {
   int p = p0 + (c >> 2);
   p = p < kOW - 1 ? p : kOW - 1;
   const __bf16* a = ps + (r * kPW + 2 * p + s0) * kC + 4 * (c & 3);
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
+  return lds_tr4(a);
 }
-
-__device__ __forceinline__ bf16x8 cat8(const s16x4& a, const s16x4& b) {
-  bf16x8 o;
-  short* q = reinterpret_cast<short*>(&o);
-  q[0] = a[0]; q[1] = a[1]; q[2] = a[2]; q[3] = a[3];
-  q[4] = b[0]; q[5] = b[1]; q[6] = b[2]; q[7] = b[3];
-  return o;
-}
-
 
 // FUSE: dz comes from the maxpool + BN+ReLU backward (MvStemPoolBwd), built per output row
 // while it is staged (512-thread workgroups): thread t < 448 owns 8 channels of the pixel
@@ -361,7 +328,7 @@ __global__ __launch_bounds__(NT, FUSE ? 4 : 1) void stem_wgrad_kernel(const __bf
   // dz rows 112..127 stay zero (written once)
   for (int q = tid; q < 16 * 8; q += NT) {
     const int r = 112 + q / 8, ch = q % 8;
-    *reinterpret_cast<u32x4*>(ds + r * 64 + ((ch ^ dswz(r)) << 3)) = u32x4{0u, 0u, 0u, 0u};
+    *reinterpret_cast<u32x4*>(ds + r * 64 + ((ch ^ tr_swz4(r)) << 3)) = u32x4{0u, 0u, 0u, 0u};
   }
   // next row's patch and dz (FUSE: z pair) in registers while the current row computes
   constexpr int kPL = (7 * 230 + NT - 1) / NT;            // 8-byte patch loads per thread
@@ -428,7 +395,7 @@ __global__ __launch_bounds__(NT, FUSE ? 4 : 1) void stem_wgrad_kernel(const __bf
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const int r = 2 * b + k;
-          *reinterpret_cast<u32x4*>(ds + r * 64 + ((ch ^ dswz(r)) << 3)) = o[k];
+          *reinterpret_cast<u32x4*>(ds + r * 64 + ((ch ^ tr_swz4(r)) << 3)) = o[k];
         }
       }
     } else {
@@ -437,7 +404,7 @@ __global__ __launch_bounds__(NT, FUSE ? 4 : 1) void stem_wgrad_kernel(const __bf
         const int q = tid + i * NT;
         if (q < kOW * 8) {
           const int r = q / 8, ch = q % 8;
-          *reinterpret_cast<u32x4*>(ds + r * 64 + ((ch ^ dswz(r)) << 3)) = pd[i];
+          *reinterpret_cast<u32x4*>(ds + r * 64 + ((ch ^ tr_swz4(r)) << 3)) = pd[i];
         }
       }
     }
@@ -446,11 +413,12 @@ __global__ __launch_bounds__(NT, FUSE ? 4 : 1) void stem_wgrad_kernel(const __bf
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int p0 = ks * 32 + 8 * g;
-      const bf16x8 af = cat8(dz_tr4(ds, p0, 16 * cw, cl), dz_tr4(ds, p0 + 4, 16 * cw, cl));
+      const bf16x8 af = cat8_copy(tr4_swz4<false>(ds, p0, 16 * cw, cl),
+                                  tr4_swz4<false>(ds, p0 + 4, 16 * cw, cl));
 #pragma unroll
       for (int tt = 0; tt < kTPW; ++tt) {
         const int t = t0 + tt, r = t >> 1, s0 = 4 * (t & 1);
-        const bf16x8 bf = cat8(px_tr4(ps, p0, r, s0, cl), px_tr4(ps, p0 + 4, r, s0, cl));
+        const bf16x8 bf = cat8_copy(px_tr4(ps, p0, r, s0, cl), px_tr4(ps, p0 + 4, r, s0, cl));
         acc[tt] = mfma(af, bf, acc[tt]);
       }
       // FUSE (4 waves / SIMD): keep the fragment reads of one k step together (hoisting
@@ -491,14 +459,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_reduce_kernel(const float* __r
 }  // namespace mv
 
 int mv_stem_wgrad_blocks(int N) {
-  static int cus = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
-      v = 256;
-    return v;
-  }();
-  int64_t g = (int64_t)cus * 4;
+  int64_t g = (int64_t)mv::num_cus() * 4;
   const int64_t rows = (int64_t)N * mv::stem::kOH;
   if (g > rows) g = rows;
   return (int)g;
