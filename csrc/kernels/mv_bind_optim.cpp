@@ -74,6 +74,14 @@ void nonfinite_scan(at::Tensor x, at::Tensor flag) {
   mv_launch_nonfinite_scan(x.data_ptr(), dtype_code(x), x.numel(), fp, cur_stream());
 }
 
+// The flat SGD / Adam / Adadelta kernels move 8 elements per lane with 16-byte accesses and
+// have no scalar fallback (the arenas hand them 64-element-aligned slices), so an offset
+// view is an error here; LARS guards its vector body itself and takes any offset.
+void check_aligned16(const char* fn, const char* what, const void* p) {
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 15u) == 0, fn, ": ", what,
+              " must be 16-byte aligned");
+}
+
 // The operands every fused step shares: the flat gradient, the fp32 master weights, the
 // optional low-precision model copy, the device hyperparameter block [lr, first, bc1, bc2]
 // (HIP-graph replays) and the skip flag.
@@ -86,14 +94,17 @@ struct StepArgs {
 };
 
 StepArgs step_args(const char* fn, const at::Tensor& g, const at::Tensor& w, const OptTensor& model,
-                   const OptTensor& dyn, const OptTensor& skip) {
+                   const OptTensor& dyn, const OptTensor& skip, bool aligned = true) {
   check_dense(fn, "grad", g, g);
+  if (aligned) check_aligned16(fn, "grad", g.data_ptr());
   StepArgs s;
   s.w = vec_ptr(fn, "master", w, g, g.numel());
+  if (aligned) check_aligned16(fn, "master", s.w);
   if (given(model)) {
     check_dense(fn, "model", *model, g);
     TORCH_CHECK(model->numel() == g.numel(), fn, ": model numel mismatch");
     s.model = model->data_ptr();
+    if (aligned) check_aligned16(fn, "model", s.model);
     s.model_dt = dtype_code(*model);
   }
   s.dyn = vec_ptr_opt(fn, "dyn", dyn, g, 4, true);
@@ -107,9 +118,10 @@ void sgd_step(at::Tensor g, at::Tensor w, c10::optional<at::Tensor> mom,
               c10::optional<at::Tensor> skip) {
   const StepArgs s = step_args("sgd_step", g, w, model, dyn, skip);
   float* mp = vec_ptr_opt("sgd_step", "momentum", mom, g, g.numel());
+  check_aligned16("sgd_step", "momentum", mp);
   c10::DeviceGuard guard(g.device());
   mv_launch_sgd(g.data_ptr(), dtype_code(g), s.w, mp, s.model, s.model_dt, g.numel(), (float)lr,
-                (float)momentum, (float)dampening, (float)wd, (float)gscale, nesterov, first,
+                (float)momentum, dampening, (float)wd, (float)gscale, nesterov, first,
                 s.dyn, s.skip, cur_stream());
 }
 
@@ -120,12 +132,14 @@ void adam_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
   const StepArgs s = step_args("adam_step", g, w, model, dyn, skip);
   float* mp = vec_ptr("adam_step", "exp_avg", m, g, g.numel());
   float* vp = vec_ptr("adam_step", "exp_avg_sq", v, g, g.numel());
+  check_aligned16("adam_step", "exp_avg", mp);
+  check_aligned16("adam_step", "exp_avg_sq", vp);
   TORCH_CHECK(step >= 1, "adam_step: step must be >= 1");
   const double bc1 = 1.0 - std::pow(b1, (double)step);
   const double bc2 = 1.0 - std::pow(b2, (double)step);
   c10::DeviceGuard guard(g.device());
   mv_launch_adam(g.data_ptr(), dtype_code(g), s.w, mp, vp, s.model, s.model_dt, g.numel(),
-                 (float)lr, (float)b1, (float)b2, (float)eps, (float)wd, (float)gscale, (float)bc1,
+                 (float)lr, b1, b2, (float)eps, (float)wd, (float)gscale, (float)bc1,
                  (float)bc2, adamw, keras_eps, s.dyn, s.skip, cur_stream());
 }
 
@@ -135,9 +149,11 @@ void adadelta_step(at::Tensor g, at::Tensor w, at::Tensor sq, at::Tensor acc,
   const StepArgs s = step_args("adadelta_step", g, w, model, dyn, skip);
   float* sp = vec_ptr("adadelta_step", "square_avg", sq, g, g.numel());
   float* ap = vec_ptr("adadelta_step", "acc_delta", acc, g, g.numel());
+  check_aligned16("adadelta_step", "square_avg", sp);
+  check_aligned16("adadelta_step", "acc_delta", ap);
   c10::DeviceGuard guard(g.device());
   mv_launch_adadelta(g.data_ptr(), dtype_code(g), s.w, sp, ap, s.model, s.model_dt, g.numel(),
-                     (float)lr, (float)rho, (float)eps, (float)wd, (float)gscale, s.dyn, s.skip,
+                     (float)lr, rho, (float)eps, (float)wd, (float)gscale, s.dyn, s.skip,
                      cur_stream());
 }
 
@@ -161,7 +177,7 @@ void lars_step(at::Tensor g, at::Tensor w, at::Tensor mom, c10::optional<at::Ten
                at::Tensor seg_nc, at::Tensor sflag, at::Tensor partial, at::Tensor norms, double lr,
                double momentum, double wd, double eta, double gscale, double eps, bool first,
                c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
-  const StepArgs s = step_args("lars_step", g, w, model, dyn, skip);
+  const StepArgs s = step_args("lars_step", g, w, model, dyn, skip, false);
   float* mp = vec_ptr("lars_step", "momentum", mom, g, g.numel());
   ChunkTable ct = make_table("lars_step", g, cbeg, clen, cseg, seg_c0, seg_nc);
   int32_t* fp = vec_ptr<int32_t>("lars_step", "sflag", sflag, g, ct.nseg, true);

@@ -30,19 +30,20 @@ void mv_launch_mt_copy(const MtArgs& a, int tensor_dtype, void* flat, int flat_d
 void mv_launch_nonfinite_scan(const void* x, int dtype, int64_t n, int* flag, hipStream_t st);
 void mv_launch_flat_cast(const void* src, int sd, void* dst, int dd, int64_t n, float scale,
                          int* found_nonfinite, hipStream_t st);
+// dampening, b1, b2 and rho arrive as doubles: their complements 1 - x are rounded to fp32 once
 void mv_launch_sgd(const void* g, int gd, float* w, float* mom, void* model, int md, int64_t n,
-                   float lr, float momentum, float dampening, float wd, float gscale, int nesterov,
+                   float lr, float momentum, double dampening, float wd, float gscale, int nesterov,
                    int first, const float* dyn, const int* skip, hipStream_t st);
 // skip (nullable): device int32; nonzero => the kernel returns without updating
 // (fp16-wire overflow guard, identical on every rank after the flag allreduce)
 // dyn (nullable): device [lr, first, bc1, bc2] read by the kernel instead of the
 // scalar arguments — HIP-graph replayable hyperparameters (mivod/torch/graphs.py)
 void mv_launch_adam(const void* g, int gd, float* w, float* m, float* v, void* model, int md,
-                    int64_t n, float lr, float b1, float b2, float eps, float wd, float gscale,
+                    int64_t n, float lr, double b1, double b2, float eps, float wd, float gscale,
                     float bc1, float bc2, int adamw, int keras_eps, const float* dyn,
                     const int* skip, hipStream_t st);
 void mv_launch_adadelta(const void* g, int gd, float* w, float* sq, float* acc, void* model, int md,
-                        int64_t n, float lr, float rho, float eps, float wd, float gscale,
+                        int64_t n, float lr, double rho, float eps, float wd, float gscale,
                         const float* dyn, const int* skip, hipStream_t st);
 void mv_launch_lars(const void* g, int gd, float* w, float* mom, void* model, int md,
                     const ChunkTable& ct, const int32_t* sflag, float* partial, float* norms,

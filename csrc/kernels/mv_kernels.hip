@@ -36,6 +36,18 @@ __device__ __forceinline__ float stored(float x) {
   else return (float)(TD)x;
 }
 
+// x * scale rounded to fp32 before the cast to the destination dtype, as
+// (t.float() * scale).to(dst) rounds: left to the compiler, the vector body folds the
+// multiply into the f16 conversion (one rounding of the exact product), which differs from
+// the scalar paths and from PyTorch wherever the fp32 product is a tie of the destination
+// (tests/test_flat_kernels_gpu.py found 8 such elements in 4096).  The empty asm makes the
+// fp32 product a value the conversion cannot look through; it emits no instruction.
+__device__ __forceinline__ float scaled(float x, float scale) {
+  float p = x * scale;
+  asm("" : "+v"(p));
+  return p;
+}
+
 template <typename TS, typename TD>
 __device__ __forceinline__ void copy_range(const TS* __restrict__ s, TD* __restrict__ d,
                                            int64_t n, float scale, int* found_nonfinite) {
@@ -47,19 +59,19 @@ __device__ __forceinline__ void copy_range(const TS* __restrict__ s, TD* __restr
       load8(s + i * kVec, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        v[j] *= scale;
+        v[j] = scaled(v[j], scale);
         if (found_nonfinite) bad |= !__builtin_isfinite(stored<TD>(v[j]));
       }
       store8(d + i * kVec, v);
     }
     for (int64_t i = nv * kVec + threadIdx.x; i < n; i += kBlock) {
-      float x = ld1(s + i) * scale;
+      float x = scaled(ld1(s + i), scale);
       if (found_nonfinite) bad |= !__builtin_isfinite(stored<TD>(x));
       st1(d + i, x);
     }
   } else {
     for (int64_t i = threadIdx.x; i < n; i += kBlock) {
-      float x = ld1(s + i) * scale;
+      float x = scaled(ld1(s + i), scale);
       if (found_nonfinite) bad |= !__builtin_isfinite(stored<TD>(x));
       st1(d + i, x);
     }
@@ -208,14 +220,18 @@ void mv_launch_nonfinite_scan(const void* x, int dt, int64_t n, int* flag, hipSt
 // -------------------------------------------------------------------------
 namespace mv {
 
-struct SgdHp { float lr, momentum, dampening, wd, gscale; int nesterov, first; };
+// The complements 1 - dampening, 1 - beta, 1 - rho (om*) are taken on the host in double and
+// rounded once: 1.f - 0.999f is off by 1.3e-5 relative (the rounding of beta2, amplified by
+// beta2 / (1 - beta2)), which put Adam's second moment 200 fp32 roundings away from torch's
+// (tests/test_flat_kernels_gpu.py).
+struct SgdHp { float lr, momentum, omd, wd, gscale; int nesterov, first; };
 // Graph-replayable hyperparameters: when ``dyn`` is non-null the kernel reads the
 // per-step values from device memory instead of its by-value launch arguments,
 // so a captured HIP graph keeps following LR schedules and step counters:
 // dyn = [lr, first (0/1), bias_correction1, bias_correction2] (fp32, 16 bytes),
 // refreshed on the stream before every replay (mivod/torch/graphs.py).
-struct AdamHp { float lr, b1, b2, eps, wd, gscale, bc1, bc2; int adamw, keras_eps; };
-struct AdadeltaHp { float lr, rho, eps, wd, gscale; };
+struct AdamHp { float lr, b1, b2, omb1, omb2, eps, wd, gscale, bc1, bc2; int adamw, keras_eps; };
+struct AdadeltaHp { float lr, rho, omr, eps, wd, gscale; };
 
 template <typename TP>
 __device__ __forceinline__ void store_model(TP* p, const float (&v)[8]) { store8(p, v); }
@@ -241,7 +257,7 @@ __global__ __launch_bounds__(kBlock) void sgd_flat_kernel(const TG* __restrict__
       for (int j = 0; j < 8; ++j) {
         float d = gv[j] * hp.gscale + hp.wd * wv[j];
         if (mom) {
-          float b = hp.first ? d : hp.momentum * mv_[j] + (1.f - hp.dampening) * d;
+          float b = hp.first ? d : hp.momentum * mv_[j] + hp.omd * d;
           mv_[j] = b;
           d = hp.nesterov ? d + hp.momentum * b : b;
         }
@@ -255,7 +271,7 @@ __global__ __launch_bounds__(kBlock) void sgd_flat_kernel(const TG* __restrict__
         float wk = w[k];
         float d = ld1(g + k) * hp.gscale + hp.wd * wk;
         if (mom) {
-          float b = hp.first ? d : hp.momentum * mom[k] + (1.f - hp.dampening) * d;
+          float b = hp.first ? d : hp.momentum * mom[k] + hp.omd * d;
           mom[k] = b;
           d = hp.nesterov ? d + hp.momentum * b : b;
         }
@@ -297,8 +313,8 @@ __global__ __launch_bounds__(kBlock) void adam_flat_kernel(const TG* __restrict_
     for (int j = 0; j < 8; ++j) {
       float gr = gv[j] * hp.gscale;
       if (!hp.adamw) gr += hp.wd * wv[j];
-      mv_[j] = hp.b1 * mv_[j] + (1.f - hp.b1) * gr;
-      vv[j] = hp.b2 * vv[j] + (1.f - hp.b2) * gr * gr;
+      mv_[j] = hp.b1 * mv_[j] + hp.omb1 * gr;
+      vv[j] = hp.b2 * vv[j] + hp.omb2 * gr * gr;
       if (hp.adamw) wv[j] *= (1.f - hp.lr * hp.wd);
       // torch: m_hat / (sqrt(v_hat) + eps); Keras/TF: lr*sqrt(bc2)/bc1 * m / (sqrt(v) + eps)
       float denom = hp.keras_eps ? (sqrtf(vv[j]) + hp.eps) * rbc2 : sqrtf(vv[j]) * rbc2 + hp.eps;
@@ -343,9 +359,9 @@ __global__ __launch_bounds__(kBlock) void adadelta_flat_kernel(const TG* __restr
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float gr = gv[j] * hp.gscale + hp.wd * wv[j];
-      sv[j] = hp.rho * sv[j] + (1.f - hp.rho) * gr * gr;
+      sv[j] = hp.rho * sv[j] + hp.omr * gr * gr;
       float delta = sqrtf(av[j] + hp.eps) / sqrtf(sv[j] + hp.eps) * gr;
-      av[j] = hp.rho * av[j] + (1.f - hp.rho) * delta * delta;
+      av[j] = hp.rho * av[j] + hp.omr * delta * delta;
       wv[j] -= hp.lr * delta;
     }
     if (cnt == kVec) {
@@ -621,29 +637,30 @@ __global__ __launch_bounds__(kBlock) void adasum_merge_kernel(const TF* fin, flo
   } while (0)
 
 void mv_launch_sgd(const void* g, int gd, float* w, float* mom, void* model, int md, int64_t n,
-                   float lr, float momentum, float dampening, float wd, float gscale, int nesterov,
+                   float lr, float momentum, double dampening, float wd, float gscale, int nesterov,
                    int first, const float* dyn, const int* skip, hipStream_t st) {
   if (n <= 0) return;
-  SgdHp hp{lr, momentum, dampening, wd, gscale, nesterov, first};
+  SgdHp hp{lr, momentum, (float)(1.0 - dampening), wd, gscale, nesterov, first};
   DISPATCH_GP(gd, md, hipLaunchKernelGGL((sgd_flat_kernel<TG, TP>), MV_GRID(n), dim3(kBlock), 0,
                                          st, (const TG*)g, w, mom, (TP*)model, n, hp, dyn, skip));
 }
 
 void mv_launch_adam(const void* g, int gd, float* w, float* m, float* v, void* model, int md,
-                    int64_t n, float lr, float b1, float b2, float eps, float wd, float gscale,
+                    int64_t n, float lr, double b1, double b2, float eps, float wd, float gscale,
                     float bc1, float bc2, int adamw, int keras_eps, const float* dyn,
                     const int* skip, hipStream_t st) {
   if (n <= 0) return;
-  AdamHp hp{lr, b1, b2, eps, wd, gscale, bc1, bc2, adamw, keras_eps};
+  AdamHp hp{lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), eps, wd, gscale,
+            bc1, bc2, adamw, keras_eps};
   DISPATCH_GP(gd, md, hipLaunchKernelGGL((adam_flat_kernel<TG, TP>), MV_GRID(n), dim3(kBlock), 0,
                                          st, (const TG*)g, w, m, v, (TP*)model, n, hp, dyn, skip));
 }
 
 void mv_launch_adadelta(const void* g, int gd, float* w, float* sq, float* acc, void* model,
-                        int md, int64_t n, float lr, float rho, float eps, float wd, float gscale,
+                        int md, int64_t n, float lr, double rho, float eps, float wd, float gscale,
                         const float* dyn, const int* skip, hipStream_t st) {
   if (n <= 0) return;
-  AdadeltaHp hp{lr, rho, eps, wd, gscale};
+  AdadeltaHp hp{lr, (float)rho, (float)(1.0 - rho), eps, wd, gscale};
   DISPATCH_GP(gd, md, hipLaunchKernelGGL((adadelta_flat_kernel<TG, TP>), MV_GRID(n), dim3(kBlock),
                                          0, st, (const TG*)g, w, sq, acc, (TP*)model, n, hp, dyn,
                                          skip));

@@ -108,10 +108,10 @@ def flat_cast(src: torch.Tensor, dst: torch.Tensor, scale: float = 1.0,
     if _on_gpu(src):
         native().flat_cast(src, dst, float(scale), nonfinite)
         return
-    v = src.float() * scale
-    if nonfinite is not None and not bool(torch.isfinite(v).all()):
+    dst.copy_(src.float() * scale)
+    # the stored values, as in the kernel and in pack (an overflow of the cast counts)
+    if nonfinite is not None and not bool(torch.isfinite(dst.float()).all()):
         nonfinite.fill_(1)
-    dst.copy_(v)
 
 
 def nonfinite_scan(x: torch.Tensor, flag: torch.Tensor) -> None:

@@ -7,6 +7,8 @@ runs before a launch (csrc/kernels/mv_checks.h).
 * GPU tier: a bad *secondary* operand (non-contiguous, wrong dtype, wrong size, other
   device) of an otherwise valid call raises.  Non-contiguous operands are ``base[::2]``
   views and wrong sizes are too large, so every pointer stays inside a live allocation.
+  The flat SGD / Adam / Adadelta steps, whose 16-byte vector body has no scalar fallback,
+  reject a ``base[1:]`` view of any operand before they launch.
 """
 import json
 import os
@@ -239,3 +241,39 @@ def test_secondary_operand_on_another_gpu_is_rejected(cuda):
     a, b, c, part = _gemm_nt_args(cuda)
     with pytest.raises(RuntimeError, match="gemm_nt: shift must be on"):
         mvk.gemm_nt(a, b, c, t(64, dtype=f32, device=other), part)
+
+
+# binding -> (the call on a dict of operands, the operands that must be 16-byte aligned)
+_STEP_CALLS = {
+    "sgd_step": (lambda o: mvk.sgd_step(o["grad"], o["master"], o["momentum"], o["model"], 0.1, 0.9,
+                                        0.0, 0.0, 1.0, False, False, None, None),
+                 ["grad", "master", "momentum", "model"]),
+    "adam_step": (lambda o: mvk.adam_step(o["grad"], o["master"], o["exp_avg"], o["exp_avg_sq"],
+                                          o["model"], 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0, 1, False,
+                                          False, None, None),
+                  ["grad", "master", "exp_avg", "exp_avg_sq", "model"]),
+    "adadelta_step": (lambda o: mvk.adadelta_step(o["grad"], o["master"], o["square_avg"],
+                                                  o["acc_delta"], o["model"], 1.0, 0.9, 1e-6, 0.0,
+                                                  1.0, None, None),
+                      ["grad", "master", "square_avg", "acc_delta", "model"]),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(_STEP_CALLS))
+def test_flat_steps_reject_unaligned_operands(cuda, name):
+    """A view one element into its allocation is contiguous and of the right size but not
+    16-byte aligned: the error fires before any launch, so no unaligned vector access runs."""
+    call, operands = _STEP_CALLS[name]
+
+    def ops():
+        return {k: t(64, dtype=bf16 if k in ("grad", "model") else f32, device=cuda)
+                for k in operands}
+
+    call(ops())
+    for bad in operands:
+        o = ops()
+        o[bad] = t(65, dtype=o[bad].dtype, device=cuda)[1:]
+        assert o[bad].is_contiguous() and o[bad].numel() == 64 and o[bad].data_ptr() % 16
+        with pytest.raises(RuntimeError, match=f"{name}: {bad} must be 16-byte aligned"):
+            call(o)
