@@ -14,11 +14,29 @@
 //     on the read; 32-bit offsets into buffer resources, out-of-range offsets read zeros).
 //     LDS = 2 K-tile buffers x 4 half-tiles (A rows of quadrant row 0 / 1, B columns
 //     of quadrant column 0 / 1) x 16 KB = 128 KB.
-//   * Each K tile runs as 4 phases, one per 64 x 32 output quadrant of the wave
-//     (16 MFMAs): the phase reads its operand half-tiles from LDS (A half 0 + B half 0,
-//     B half 1, A half 1, nothing), issues one half-tile of the NEXT K tile into the
-//     other buffer, and waits (counted vmcnt, never 0 in the steady state) for the
-//     half-tile the next phase reads.
+//   * A K tile's 64 MFMAs run in one of three loop forms, fixed per mode at its measured
+//     winner (same-box A/B, profiles/r5_ab_log.md; the forms are bitwise equal, each
+//     accumulator seeing the same MFMA sequence):
+//       - 4 phases, one per 64 x 32 output quadrant of the wave (16 MFMAs): the phase
+//         reads its operand half-tiles from LDS (A half 0 + B half 0, B half 1, A half 1,
+//         nothing), issues one half-tile of the NEXT K tile into the other buffer, and
+//         waits (counted vmcnt, never 0 in the steady state) for the half-tile the next
+//         phase reads.  Every GEMM mode but the implicit 3x3 ones (AMODE 0 / 1 / 2): the
+//         1x1 GEMMs lose 3-5% on 2 phases, whose phase-0 read section carries 16 fragment
+//         reads plus 6 LDS-DMA issues while the other wave group runs 32 MFMAs, and whose
+//         last K tile pays an un-overlapped vmcnt(0) before every epilogue (K = 256 is
+//         only 4 K tiles); with the DMA among the MFMAs they still lose (456 -> 476 us).
+//       - 2 phases of 32 MFMAs (4 barriers per K tile instead of 8), the next K tile's
+//         LDS-DMA issued in the read sections with counted waits: the 1x1 and strided
+//         weight gradients (wgrad256_kernel TAPS 1 / 2).  Every weight gradient gains
+//         4-13% over 4 phases.
+//       - 2 phases with the LDS-DMA pieces spread among the MFMAs ("DM"), each read
+//         section retiring what it needs with vmcnt(0): the implicit 3x3 modes (AMODE
+//         3 / 4: +5-9% from 2 phases, another 5-11% from DM, whose read sections no
+//         longer carry the issue cost) and the 3x3 weight gradient (TAPS 9: level to
+//         -4%).  The HBM-bound 1x1 weight gradients lose 4% with DM: their DMA lands a
+//         section later and the reads wait for it.
+//     (Tried and not kept: DM in the 4-phase loop — 256 VGPRs and scratch spills.)
 //   * Persistent (one workgroup per CU): one stream of K tiles runs over all of a
 //     workgroup's output tiles, so the next tile's first K tile is staged during the
 //     current tile's last one and its epilogue (short-K shapes: K = 256 is 4 K tiles).
@@ -68,26 +86,6 @@ __device__ __forceinline__ void barrier() {
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// Diagnostic build only (scripts/debug/g256_stamps.hip defines MV_G256_STAMPS): lane 0 of
-// every wave of workgroup 0 writes the shader clock at 13 points of the 2-phase K loop of
-// K tiles 8..11 of its first output tile into g_g256_stamps (vector stores; never in the
-// shipped module, where the macro expands to nothing).
-#ifdef MV_G256_STAMPS
-__device__ uint64_t g_g256_stamps[8 * 4 * 16];
-#define G256_STAMP(i)                                                                      \
-  do {                                                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                     \
-    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && stamp_tile && kt >= 8 && kt < 12)    \
-      g_g256_stamps[((threadIdx.x >> 6) * 4 + (kt - 8)) * 16 + (i)] =                      \
-          __builtin_amdgcn_s_memtime();                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                     \
-  } while (0)
-#else
-#define G256_STAMP(i) \
-  do {                \
-  } while (0)
-#endif
-
 // Kernel arguments.  A modes: 0 plain A[M, K]; 1 strided gather (a stride-ds 1x1 conv:
 // A is the [*, H, W, K] input, output row (n, ho, wo) reads input row (n, ho ds, wo ds));
 // 2 dual source (A columns [0, K1) from A [M, K1], [K1, K) from A2 [M, K - K1]);
@@ -133,6 +131,18 @@ struct Args {
   const __bf16* bias16;           // EPI 7: the bf16 bias (instead of badd)
 };
 
+// Output row r of an [*, Ho, Wo] image -> its pixel (n, ho, wo).  Rows < 2^31: unsigned
+// 32-bit divisions.
+struct Pixel {
+  uint32_t n, ho, wo;
+};
+__device__ __forceinline__ Pixel pixel_of(uint32_t r, int Ho, int Wo) {
+  const uint32_t hw = (uint32_t)(Ho * Wo);
+  const uint32_t n = r / hw, rem = r - n * hw;
+  const uint32_t ho = rem / (uint32_t)Wo;
+  return Pixel{n, ho, rem - ho * (uint32_t)Wo};
+}
+
 template <int EPI>
 constexpr int nvec() { return EPI == 1 ? 1 : EPI == 4 ? 4 : (EPI == 6 || EPI == 7) ? 1 : 0; }
 constexpr int kVecFloats = 8192;          // LDS for the per-channel epilogue vectors (32 KB)
@@ -142,8 +152,11 @@ constexpr int kVecFloats = 8192;          // LDS for the per-channel epilogue ve
 // CUs for every N tile count, where 256-row blocks leave a 1/8- to 1/2-full last round).
 // With MT = 7 the second A half-tile holds 48 live rows (the other 16 re-stage live rows,
 // never read).
-template <int EPI, int AMODE, int MT, bool PH2, bool DM = false>
+template <int EPI, int AMODE, int MT>
 __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
+  // the K-loop form is a property of the mode (file header): the implicit 3x3 modes run
+  // the 2-phase loop with the LDS-DMA among the MFMAs, every other mode the 4-phase loop
+  constexpr bool DM = AMODE == 3 || AMODE == 4;
   constexpr int BMv = MT * 32;
   constexpr int MH1 = MT - 4;               // m tiles in A half 1
   constexpr int NV = nvec<EPI>();
@@ -204,17 +217,15 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
                       ((h == 1 && rr >= 16 * MH1) ? rr - 16 * MH1 : rr);
         row = row < p.M ? row : p.M - 1;           // rows past M: a valid row, never stored
         if constexpr (AMODE == 1) {          // rows < 2^31: 32-bit unsigned divisions
-          const uint32_t hw = (uint32_t)(p.Ho * p.Wo), r32 = (uint32_t)row;
-          const int64_t n = r32 / hw;
-          const int rem = (int)(r32 - (uint32_t)n * hw);
-          const int ho = (int)((uint32_t)rem / (uint32_t)p.Wo), wo = rem - ho * p.Wo;
+          const Pixel px = pixel_of((uint32_t)row, p.Ho, p.Wo);
+          const int64_t n = px.n;
+          const int ho = (int)px.ho, wo = (int)px.wo;
           row = (n * p.H + (int64_t)ho * p.ds) * p.W + (int64_t)wo * p.ds;
         }
         if constexpr (AMODE == 3) {          // rows < 2^31: 32-bit unsigned divisions
-          const uint32_t hw = (uint32_t)(p.Ho * p.Wo), r32 = (uint32_t)row;
-          const int64_t n = r32 / hw;
-          const int rem = (int)(r32 - (uint32_t)n * hw);
-          const int ho = (int)((uint32_t)rem / (uint32_t)p.Wo), wo = rem - ho * p.Wo;
+          const Pixel px = pixel_of((uint32_t)row, p.Ho, p.Wo);
+          const int64_t n = px.n;
+          const int ho = (int)px.ho, wo = (int)px.wo;
           const int pad = p.ks >> 1;
           const int hi0 = ho * p.ds - pad, wi0 = wo * p.ds - pad;
           uint32_t v = 0;
@@ -233,7 +244,8 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
         }
         if constexpr (AMODE == 4) {
           // class row (n, ci, cj) reads dy (n, ci + di, cj + dj), di, dj in {0, 1}: bit
-          // 2 di + dj set when that pixel is inside dy
+          // 2 di + dj set when that pixel is inside dy.  (Only (ci, cj), no image index;
+          // written out because pixel_of here changes the MT = 7 kernel's instructions.)
           const uint32_t hw = (uint32_t)(p.Ho * p.Wo);
           const int rem = (int)((uint32_t)row % hw);
           const int ci = (int)((uint32_t)rem / (uint32_t)p.Wo), cj = rem - ci * p.Wo;
@@ -247,10 +259,9 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
           offa[h][i] = (uint32_t)(row * (p.K1 * 2)) + scb;
           int64_t row2 = row;
           if (p.ds > 1) {          // A2 = x [*, H, W, K2] read at the output row's stride pixel
-            const uint32_t hw = (uint32_t)(p.Ho * p.Wo), r32 = (uint32_t)row;
-            const int64_t n = r32 / hw;
-            const int rem = (int)(r32 - (uint32_t)n * hw);
-            const int ho = (int)((uint32_t)rem / (uint32_t)p.Wo), wo = rem - ho * p.Wo;
+            const Pixel px = pixel_of((uint32_t)row, p.Ho, p.Wo);
+            const int64_t n = px.n;
+            const int ho = (int)px.ho, wo = (int)px.wo;
             row2 = (n * p.H + (int64_t)ho * p.ds) * p.W + (int64_t)wo * p.ds;
           }
           offa2[h][i] = (uint32_t)(row2 * ((p.K - p.K1) * 2)) + scb;
@@ -413,10 +424,8 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
     if constexpr (AMODE != 4) {
       return row;
     } else {
-      const uint32_t hw = (uint32_t)(p.Ho * p.Wo), r32 = (uint32_t)row;
-      const uint32_t n = r32 / hw, rem = r32 - n * hw;
-      const uint32_t ci = rem / (uint32_t)p.Wo, cj = rem - ci * (uint32_t)p.Wo;
-      return ((int64_t)n * p.H + 2 * ci + p.ph) * p.W + 2 * cj + p.pw;
+      const Pixel px = pixel_of((uint32_t)row, p.Ho, p.Wo);
+      return ((int64_t)px.n * p.H + 2 * px.ho + p.ph) * p.W + 2 * px.wo + p.pw;
     }
   };
   auto epilogue = [&](int64_t tl) {
@@ -598,7 +607,7 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
   issue(2, 0, 0);
   issue(3, 0, 0);
   issue(1, 0, 0);
-  if constexpr (PH2) wait_vm<2>();  // A0 + B0 + B1 retired (phase 0 reads all three)
+  if constexpr (DM) wait_vm<2>();   // A0 + B0 + B1 retired (phase 0 reads all three)
   else wait_vm<4>();
   barrier();
   if (wm == 1) barrier();          // the one-barrier stagger of wave group 1
@@ -608,17 +617,20 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
   int buf = 0;
   bool after = false;              // an epilogue ran since the last wait: nothing to retire
   int64_t ntile = tile + G;
-#ifdef MV_G256_STAMPS
-  bool stamp_tile = true;
-#endif
   for (;;) {
     const bool last_k = kt + 1 == KT;
     const bool more = !last_k || ntile < p.ntiles;
     const int nkt = last_k ? 0 : kt + 1;
     const int nb = buf ^ 1;
     if (last_k && more) set_src(ntile);
-    if constexpr (PH2 && DM) {
-      // 2-phase loop with the next K tile's LDS-DMA inside the MFMA sections: phase 0's
+    if constexpr (DM) {
+      // Two phases of 32 MFMAs per K tile (4 barriers instead of 8).  Hazard rule under
+      // the one-barrier stagger (wave group 1's program barrier j is group 0's j + 1):
+      // a half-tile is read only after the program barrier FOLLOWING the one its wait
+      // preceded, and re-staged only 2 program barriers after the barrier its reads
+      // preceded.  Program barriers of K tile kt: 4kt (after phase 0's reads),
+      // 4kt + 1 (after its MFMAs), 4kt + 2, 4kt + 3.
+      // The next K tile's LDS-DMA goes inside the MFMA sections: phase 0's
       // section issues A0' B0' B1' (their buffer's last reads preceded 4kt - 4: free after
       // 4kt - 2), phase 1's issues A1' (free after 4kt); each read section retires, with
       // vmcnt(0), the half-tiles it reads after the next barrier (A1 in phase 0, A0' B0'
@@ -640,119 +652,65 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
       mma_dm(1, 1, 1, 0, 2, 10, [&](int j) { issue_k(1, nb, nkt, ki, j); });
       barrier();
       if (last_k) wait_vm<0>();
-    } else if constexpr (PH2) {
-      // Two phases of 32 MFMAs per K tile (4 barriers instead of 8).  Hazard rule under
-      // the one-barrier stagger (wave group 1's program barrier j is group 0's j + 1):
-      // a half-tile is read only after the program barrier FOLLOWING the one its wait
-      // preceded, and re-staged only 2 program barriers after the barrier its reads
-      // preceded.  Program barriers of K tile kt: 4kt (after phase 0's reads),
-      // 4kt + 1 (after its MFMAs), 4kt + 2, 4kt + 3.
-      // phase 0: reads A0 + B0 + B1 (read 4 kt - 3 .. kt - 1's waits: ok), issues A0' B0'
-      // B1' (their last reads preceded 4kt - 4: free after 4kt - 2), retires A1 (read
-      // after 4kt + 1)
-      G256_STAMP(0);
+    } else {
+      // Steady state: phase q issues one half-tile of the next K tile (A0', B0', B1', A1')
+      // and retires, by a counted wait, the half-tile phase q + 1 reads.  Before a tile's
+      // epilogue (last_k && more) the next tile's four half-tiles go out in phases 0-1 and
+      // are all retired in phase 3 — the epilogue's stores are then never inside a count.
+      // phase 0: quadrant (0, 0) — reads A0 + B0, retires B1
       read_a(buf, 0);
       read_b(buf, 0);
-      read_b(buf, 1);
-      G256_STAMP(1);
-      if (more) {
+      if (!more) {
+        wait_vm<2>();
+      } else if (last_k) {
         issue(0, nb, nkt);
         issue(2, nb, nkt);
-        issue(3, nb, nkt);
-        G256_STAMP(2);
-        if (!after) wait_vm<6>();
-      } else if (!after) {
-        wait_vm<0>();
-      }
-      G256_STAMP(3);
-      barrier();
-      G256_STAMP(4);
-      mma(0, 0);
-      mma(0, 1);
-      G256_STAMP(5);
-      barrier();
-      G256_STAMP(6);
-      // phase 1: reads A1, issues A1' (its last reads preceded 4kt - 2: free after 4kt),
-      // retires A0' B0' B1' (read after 4kt + 3); before an epilogue everything (the
-      // epilogue's stores are then never inside a count)
-      read_a(buf, 1);
-      G256_STAMP(7);
-      if (more) {
-        issue(1, nb, nkt);
-        G256_STAMP(8);
-        if (last_k) wait_vm<0>();
-        else wait_vm<2>();
-      }
-      G256_STAMP(9);
-      barrier();
-      G256_STAMP(10);
-      mma(1, 1);
-      mma(1, 0);
-      G256_STAMP(11);
-      barrier();
-      G256_STAMP(12);
-    } else {
-    // Steady state: phase q issues one half-tile of the next K tile (A0', B0', B1', A1')
-    // and retires, by a counted wait, the half-tile phase q + 1 reads.  Before a tile's
-    // epilogue (last_k && more) the next tile's four half-tiles go out in phases 0-1 and
-    // are all retired in phase 3 — the epilogue's stores are then never inside a count.
-    // phase 0: quadrant (0, 0) — reads A0 + B0, retires B1
-    read_a(buf, 0);
-    read_b(buf, 0);
-    if (!more) {
-      wait_vm<2>();
-    } else if (last_k) {
-      issue(0, nb, nkt);
-      issue(2, nb, nkt);
-      wait_vm<4>();
-    } else {
-      issue(0, nb, nkt);
-      if (!after) wait_vm<4>();
-    }
-    barrier();
-    mma(0, 0);
-    barrier();
-    // phase 1: quadrant (0, 1) — reads B1, retires A1
-    read_b(buf, 1);
-    if (!more) {
-      wait_vm<0>();
-    } else if (last_k) {
-      issue(3, nb, nkt);
-      issue(1, nb, nkt);
-      wait_vm<8>();
-    } else {
-      issue(2, nb, nkt);
-      if (!after) wait_vm<4>();
-    }
-    barrier();
-    mma(0, 1);
-    barrier();
-    // phase 2: quadrant (1, 1) — reads A1
-    read_a(buf, 1);
-    if (more && !last_k) issue(3, nb, nkt);
-    barrier();
-    mma(1, 1);
-    barrier();
-    // phase 3: quadrant (1, 0) — no reads (B0 kept in registers); retires A0' + B0'
-    if (more) {
-      if (last_k) {
-        wait_vm<0>();
-      } else {
-        issue(1, nb, nkt);
         wait_vm<4>();
+      } else {
+        issue(0, nb, nkt);
+        if (!after) wait_vm<4>();
       }
-    }
-    barrier();
-    mma(1, 0);
-    barrier();
+      barrier();
+      mma(0, 0);
+      barrier();
+      // phase 1: quadrant (0, 1) — reads B1, retires A1
+      read_b(buf, 1);
+      if (!more) {
+        wait_vm<0>();
+      } else if (last_k) {
+        issue(3, nb, nkt);
+        issue(1, nb, nkt);
+        wait_vm<8>();
+      } else {
+        issue(2, nb, nkt);
+        if (!after) wait_vm<4>();
+      }
+      barrier();
+      mma(0, 1);
+      barrier();
+      // phase 2: quadrant (1, 1) — reads A1
+      read_a(buf, 1);
+      if (more && !last_k) issue(3, nb, nkt);
+      barrier();
+      mma(1, 1);
+      barrier();
+      // phase 3: quadrant (1, 0) — no reads (B0 kept in registers); retires A0' + B0'
+      if (more) {
+        if (last_k) {
+          wait_vm<0>();
+        } else {
+          issue(1, nb, nkt);
+          wait_vm<4>();
+        }
+      }
+      barrier();
+      mma(1, 0);
+      barrier();
     }
     buf = nb;
     after = last_k;
     if (last_k) {
       if constexpr (!(MV_G256_DIAG & 32)) epilogue(tile);
-#ifdef MV_G256_STAMPS
-      stamp_tile = false;
-#endif
       if (!more) break;
       tile = ntile;
       ntile += G;
@@ -785,7 +743,8 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(Args p) {
 // 32-lane half reads ({r..r+3, r+8..r+11}) over the 8 distinct 32-B bank windows.
 // MFMA A = X^T (c rows), B = DY (k columns): a lane's accumulators are 4 consecutive
 // c of one k — 16-byte partial stores.  Waves 2 (c) x 4 (k), 128 c x 64 k per wave, the
-// 4-phase / one-barrier-stagger K loop of gemm256_kernel.
+// one-barrier stagger of gemm256_kernel over a 2-phase K loop: 4 to 13% faster than the
+// 4-phase form on every weight gradient (profiles/r5_ab_log.md).
 // ===========================================================================
 
 struct WArgs {
@@ -814,8 +773,12 @@ __device__ __forceinline__ bf16x8 trp(const __bf16* pa, const __bf16* pb) {
   return cat8_shuffle(a, b);
 }
 
-template <int TAPS, bool PH2, bool DM = false>
+template <int TAPS>
 __global__ __launch_bounds__(NT, 1) void wgrad256_kernel(WArgs p) {
+  // LDS-DMA among the MFMAs for the 3x3 weight gradient only (7x7x512 -4%, 14x14x256
+  // level); the HBM-bound 1x1 and strided ones lose with it (+4%: their DMA lands a section
+  // later and the reads wait for it) and run the plain 2-phase loop — profiles/r5_ab_log.md
+  constexpr bool DM = TAPS == 9;
   __shared__ __attribute__((aligned(16))) __bf16 smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -990,7 +953,7 @@ __global__ __launch_bounds__(NT, 1) void wgrad256_kernel(WArgs p) {
     __builtin_amdgcn_s_setprio(0);
   };
 
-  if (KT > 0 && PH2 && DM) {
+  if (KT > 0 && DM) {
     // the 2-phase loop with the next K tile's LDS-DMA among the MFMAs (gemm256_kernel DM:
     // same hazard rule, each read section retires its half-tiles with vmcnt(0); past the
     // last K tile the pieces read rows beyond the split — zeros into the idle buffer)
@@ -1018,8 +981,11 @@ __global__ __launch_bounds__(NT, 1) void wgrad256_kernel(WArgs p) {
     }
     wait_vm<0>();
     if (wc == 0) barrier();
-  } else if (KT > 0 && PH2) {
-    // the two-phase K loop of gemm256_kernel (PH2: same hazard rule)
+  } else if (KT > 0) {
+    // the plain 2-phase loop (gemm256_kernel DM: same hazard rule): each read section
+    // issues the next K tile's half-tiles itself — phase 0 A0' B0' B1', phase 1 A1' — and
+    // retires by a counted wait the half-tiles read after the next barrier (A1: vmcnt 6
+    // leaves phase 0's three in flight; A0' B0' B1': vmcnt 2 leaves A1')
     issue(0, 0, 0);
     issue(2, 0, 0);
     issue(3, 0, 0);
@@ -1056,52 +1022,6 @@ __global__ __launch_bounds__(NT, 1) void wgrad256_kernel(WArgs p) {
       barrier();
     }
     if (wc == 0) barrier();
-  } else if (KT > 0) {
-    issue(0, 0, 0);
-    issue(2, 0, 0);
-    issue(3, 0, 0);
-    issue(1, 0, 0);
-    wait_vm<4>();
-    barrier();
-    if (wc == 1) barrier();
-    for (int kt = 0; kt < KT; ++kt) {
-      const int buf = kt & 1, nb = buf ^ 1;
-      const bool more = kt + 1 < KT;
-      read_a(buf, 0);
-      read_b(buf, 0);
-      if (more) {
-        issue(0, nb, kt + 1);
-        wait_vm<4>();
-      } else {
-        wait_vm<2>();
-      }
-      barrier();
-      mma(0, 0);
-      barrier();
-      read_b(buf, 1);
-      if (more) {
-        issue(2, nb, kt + 1);
-        wait_vm<4>();
-      } else {
-        wait_vm<0>();
-      }
-      barrier();
-      mma(0, 1);
-      barrier();
-      read_a(buf, 1);
-      if (more) issue(3, nb, kt + 1);
-      barrier();
-      mma(1, 1);
-      barrier();
-      if (more) {
-        issue(1, nb, kt + 1);
-        wait_vm<4>();
-      }
-      barrier();
-      mma(1, 0);
-      barrier();
-    }
-    if (wc == 0) barrier();
   }
   // partial[split][k][c .. c + 3] (zeros for an empty split)
   float* pp = p.partial + (int64_t)split * p.K * p.C;
@@ -1117,15 +1037,15 @@ __global__ __launch_bounds__(NT, 1) void wgrad256_kernel(WArgs p) {
 }  // namespace g256
 }  // namespace mv
 
-// MIVOD_G256: comma-separated A/B / diagnostic switches of this file — ph2 / ph4 (K-loop
-// form everywhere), dm / nodm (LDS-DMA inside the 2-phase loop's MFMA sections), bm224 /
-// bm256 / bmcost (row-block height), trace (one stderr line per launch).  Read once.
-static bool g256_opt(const char* tok) {
-  static const std::string v = [] {
+// MIVOD_G256=trace: one stderr line per launch (mode, shape, grid) — to attach shapes to a
+// rocprofv3 kernel trace of the same run (launch order is the same; scripts/g256_launches.py).
+// Read once.
+static bool g256_trace() {
+  static const bool v = [] {
     const char* e = std::getenv("MIVOD_G256");
-    return std::string(",") + (e ? e : "") + ",";
+    return e && std::string(e) == "trace";
   }();
-  return v.find(std::string(",") + tok + ",") != std::string::npos;
+  return v;
 }
 
 // Row-block height: 224 (MT = 7) when the blocks tile M exactly and there is one column tile
@@ -1135,23 +1055,7 @@ static bool g256_opt(const char* tok) {
 // vs 896 = 4 rounds of 224) measured level on bench.py and 1-2% slower on those shapes
 // (profiles/r5_ab_log.md): a 224-row tile takes about as long as a 256-row one, the K loop's
 // time being set by the B staging, the fragment reads and the barriers, not by A's rows.
-// MIVOD_G256=bm256 / bm224 forces one height, =bmcost that model (A/B runs).
-static int g256_bm(int64_t M, int N) {
-  static const int force =
-      g256_opt("bm224") ? 224 : g256_opt("bm256") ? 256 : g256_opt("bmcost") ? -1 : 0;
-  if (force == 224 || force == 256) return force;
-  if (force == -1) {
-    const int64_t ntn = N / mv::g256::BN, cus = mv::num_cus();
-    auto cost = [&](int64_t bm) {
-      const int64_t tiles = (M + bm - 1) / bm * ntn;
-      int64_t g = (tiles < cus ? tiles : cus) / ntn * ntn;
-      g = g > ntn ? g : ntn;
-      return (tiles + g - 1) / g * bm;
-    };
-    return cost(224) * 100 < cost(256) * 97 ? 224 : 256;
-  }
-  return N == 256 && M % 224 == 0 ? 224 : 256;
-}
+static int g256_bm(int64_t M, int N) { return N == 256 && M % 224 == 0 ? 224 : 256; }
 
 bool mv_gemm256_supported(int64_t M, int N, int K) {
   return M > 0 && N % 256 == 0 && K % 64 == 0 && K >= 64 &&
@@ -1173,32 +1077,6 @@ int64_t mv_gemm256_partials(int64_t M, int N) {
   return 2 * (g256_grid(M, N) / (N / mv::g256::BN));
 }
 
-// K-loop form of the 256 x 256 pipeline: 2 phases of 32 MFMAs per K tile (PH2) or 4 of
-// 16.  Same-box A/B (scripts/micro_g256_ph.py, profiles/r5_ab_log.md): PH2 wins on the
-// implicit 3x3 convolutions (AMODE 3 / 4: +5..9%) and every weight gradient (+4..13%) and
-// loses on the plain / strided / dual-source 1x1 GEMMs (-3..5%), so it is chosen per mode;
-// MIVOD_G256=ph2 / ph4 forces one form everywhere (A/B runs).
-static int g256_ph_env() {
-  static const int v = g256_opt("ph2") ? 2 : g256_opt("ph4") ? 4 : 0;
-  return v;
-}
-static bool g256_ph2(bool prefer) {
-  const int v = g256_ph_env();
-  return v ? v == 2 : prefer;
-}
-// LDS-DMA inside the MFMA sections of the 2-phase loop (MIVOD_G256=dm / nodm force it)
-static bool g256_dm(bool prefer) {
-  static const int v = g256_opt("dm") ? 1 : g256_opt("nodm") ? -1 : 0;
-  return v ? v > 0 : prefer;
-}
-
-// MIVOD_G256=trace: one stderr line per launch (mode, shape, grid) — to attach shapes to a
-// rocprofv3 kernel trace of the same run (launch order is the same)
-static bool g256_trace() {
-  static const bool v = g256_opt("trace");
-  return v;
-}
-
 template <int EPI, int AMODE>
 static void g256_launch(mv::g256::Args a, hipStream_t st) {
   using namespace mv::g256;
@@ -1209,17 +1087,8 @@ static void g256_launch(mv::g256::Args a, hipStream_t st) {
   a.ntn = a.N / BN;
   a.ntiles = (a.M + bm - 1) / bm * a.ntn;
   const dim3 grid((unsigned)g256_grid(a.M, a.N));
-  const bool ph2 = g256_ph2(AMODE == 3 || AMODE == 4);
-  const bool dm = ph2 && g256_dm(AMODE == 3 || AMODE == 4);
-  if (bm == 224) {
-    if (dm) hipLaunchKernelGGL((gemm256_kernel<EPI, AMODE, 7, true, true>), grid, dim3(NT), 0, st, a);
-    else if (ph2) hipLaunchKernelGGL((gemm256_kernel<EPI, AMODE, 7, true>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((gemm256_kernel<EPI, AMODE, 7, false>), grid, dim3(NT), 0, st, a);
-  } else {
-    if (dm) hipLaunchKernelGGL((gemm256_kernel<EPI, AMODE, 8, true, true>), grid, dim3(NT), 0, st, a);
-    else if (ph2) hipLaunchKernelGGL((gemm256_kernel<EPI, AMODE, 8, true>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((gemm256_kernel<EPI, AMODE, 8, false>), grid, dim3(NT), 0, st, a);
-  }
+  if (bm == 224) hipLaunchKernelGGL((gemm256_kernel<EPI, AMODE, 7>), grid, dim3(NT), 0, st, a);
+  else hipLaunchKernelGGL((gemm256_kernel<EPI, AMODE, 8>), grid, dim3(NT), 0, st, a);
 }
 
 template <int TAPS>
@@ -1229,13 +1098,7 @@ static void w256_launch(const mv::g256::WArgs& a, hipStream_t st) {
   if (g256_trace())
     std::fprintf(stderr, "[g256] wgrad256 TAPS %d M %lld C %d K %d k1 %d Cx %d H %d W %d ds %d grid %u\n",
                  TAPS, (long long)a.M, a.C, a.K, a.k1, a.Cx, a.H, a.W, a.ds, grid.x);
-  // DM for the 3x3 weight gradient (7x7x512 -4%, 14x14x256 level); the HBM-bound 1x1 ones
-  // lose with it (+4%: their DMA lands a section later and the reads wait for it)
-  const bool ph2 = g256_ph2(true);
-  if (ph2 && g256_dm(TAPS == 9))
-    hipLaunchKernelGGL((wgrad256_kernel<TAPS, true, true>), grid, dim3(NT), 0, st, a);
-  else if (ph2) hipLaunchKernelGGL((wgrad256_kernel<TAPS, true>), grid, dim3(NT), 0, st, a);
-  else hipLaunchKernelGGL((wgrad256_kernel<TAPS, false>), grid, dim3(NT), 0, st, a);
+  hipLaunchKernelGGL((wgrad256_kernel<TAPS>), grid, dim3(NT), 0, st, a);
 }
 
 bool mv_gemm256_nt(const void* A, const void* B, void* C, int64_t M, int N, int K,

@@ -1,8 +1,7 @@
-"""mivod's BERT-shape weight gradients (mv_gemm256.hip wgrad256_kernel) alone, for A/B
-of the K-loop forms (run under MIVOD_G256=ph2 / ph4 / dm / nodm) and for PMC
-passes; --zeros runs zero-filled operands (the DVFS check: the same instruction stream at
-the clock the chip holds without data toggling), --blaslt adds hipBLASLt's forward GEMM of
-the same FLOPs as a reference.
+"""mivod's BERT-shape weight gradients (mv_gemm256.hip wgrad256_kernel) alone, for timing
+and for PMC passes; --zeros runs zero-filled operands (the DVFS check: the same instruction
+stream at the clock the chip holds without data toggling), --blaslt adds hipBLASLt's forward
+GEMM of the same FLOPs as a reference.
     python scripts/micro_wgrad_modes.py [--iters 20] [--shape 3072x1024] [--zeros] [--blaslt]"""
 import argparse
 import os
@@ -35,7 +34,7 @@ def timeit(tag, fn, N, Kd):
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / a.iters * 1000.0
-    print(f"{os.environ.get('MIVOD_G256', '-'):6s} {tag:10s} {'zeros' if a.zeros else 'randn'} "
+    print(f"{tag:10s} {'zeros' if a.zeros else 'randn'} "
           f"[{N} x {Kd}] over {T}: {us:7.1f} us ({2.0 * T * N * Kd / us / 1e6:5.0f} TF/s)",
           flush=True)
 

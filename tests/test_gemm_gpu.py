@@ -465,7 +465,8 @@ def test_resnet_bn_recompute_matches_materialised(cuda, monkeypatch):
 
 
 @pytest.mark.parametrize("K1,K2", [(256, 64), (512, 128), (1024, 256), (2048, 512)])
-@pytest.mark.parametrize("M", [1, 64 * 3 + 5, 4096 + 17, 70000])
+# M = 448 with K2 = 256: mv_gemm256.hip's 224-row blocks (MT = 7)
+@pytest.mark.parametrize("M", [1, 64 * 3 + 5, 448, 4096 + 17, 70000])
 def test_gemm_fold_dx_matches_fp32(cuda, M, K1, K2):
     """Dual-source fold data gradient + BN2 ReLU-backward reduce epilogue vs fp32 math."""
     nat = _nat()
@@ -783,7 +784,9 @@ def test_gemm_dual_bias_256(cuda, M, K1, K2):
 
 @pytest.mark.parametrize("n,c,h,k,s", [(2, 256, 9, 512, 2), (8, 512, 28, 1024, 2),
                                        (3, 1024, 14, 2048, 2), (2, 512, 7, 256, 1),
-                                       (1, 64, 5, 256, 3)])
+                                       (1, 64, 5, 256, 3),
+                                       # M = 28 x 4 x 4 = 448, N = 256: 224-row blocks (MT = 7)
+                                       (28, 64, 7, 256, 2)])
 def test_conv1x1_strided_stats(cuda, n, c, h, k, s):
     """Strided 1x1 conv (rows gathered at the stride) + BN statistics on mv_gemm256.hip."""
     nat = _nat()

@@ -63,7 +63,8 @@ def test_bert_layer_uses_mivod_weight_gradient(cuda, monkeypatch):
 
 
 @pytest.mark.parametrize("split", [False, True])
-@pytest.mark.parametrize("T,nin,nout", [(4096 + 17, 4096, 1024), (333, 1024, 256), (2048, 256, 64)])
+@pytest.mark.parametrize("T,nin,nout", [(4096 + 17, 4096, 1024), (333, 1024, 256), (2048, 256, 64),
+                                        (448, 256, 64)])   # nin 256, T % 224 == 0: 224-row tiles
 def test_gelu_linear_fused_backward_matches_fp32(cuda, monkeypatch, T, nin, nout, split):
     """BERT's FFN tail y = gelu(pre + b) W^T: the down projection's data gradient with the
     bias-GELU backward in the GEMM epilogue (mv_gemm256.hip EPI 7; split=True: hipBLASLt's
