@@ -1,9 +1,10 @@
-// mivod._mvk bindings: fused NHWC BatchNorm, pooling and the ResNet stem
-// (mv_bn.h, mv_pool.h, mv_stem.h)
+// mivod._mvk bindings: fused NHWC BatchNorm, SyncBatchNorm, pooling and the ResNet stem
+// (mv_bn.h, mv_syncbn.h, mv_pool.h, mv_stem.h)
 #include "mv_checks.h"
 #include "mv_bn.h"
 #include "mv_pool.h"
 #include "mv_stem.h"
+#include "mv_syncbn.h"
 
 namespace {
 using namespace mvc;
@@ -281,6 +282,157 @@ std::vector<at::Tensor> bn_bwd_from_partials(at::Tensor dz, at::Tensor x, at::Te
 }
 
 // ---------------------------------------------------------------------------
+// SyncBatchNorm (mv_syncbn.h): the local passes and the kernels around the two collectives
+// ---------------------------------------------------------------------------
+// int32 [N, 3C + 4] gathered statistics records -> N, sets *C
+int check_records(const char* fn, const at::Tensor& recs, const at::Tensor& like, int64_t* C) {
+  check_nd(fn, "records", recs, like, 2, at::kInt);
+  const int64_t w = recs.size(1);
+  TORCH_CHECK(recs.size(0) > 0 && recs.size(0) < (int64_t(1) << 20) && w > 4 && (w - 4) % 24 == 0,
+              fn, ": records must be int32 [N, 3 C + 4] with C % 8 == 0");
+  *C = (w - 4) / 3;
+  return (int)recs.size(0);
+}
+
+// {record int32 [3C + 4], P}: this rank's statistics pass around shift and its record;
+// P = the [2][C] partial rows the pass produced
+std::tuple<at::Tensor, int64_t> syncbn_stats(at::Tensor x, c10::optional<at::Tensor> shift) {
+  const char* fn = "syncbn_stats";
+  int64_t C;
+  const int64_t M = check_act(fn, "x", x, x, &C);
+  TORCH_CHECK(M > 0, fn, ": empty input");
+  const float* sp = vec_ptr_opt(fn, "shift", shift, x, C);
+  c10::DeviceGuard guard(x.device());
+  const int P = mv_bn_partials(M, (int)C);
+  at::Tensor partial = at::empty({(int64_t)P * 2 * C}, x.options().dtype(at::kFloat));
+  at::Tensor rec = at::empty({mv_syncbn_record_words((int)C)}, x.options().dtype(at::kInt));
+  const int pa = mv_bn_stats_pass(x.data_ptr(), M, (int)C, sp, partial.data_ptr<float>(), P,
+                                  cur_stream());
+  mv_syncbn_record(partial.data_ptr<float>(), pa, M, (int)C, sp, rec.data_ptr<int32_t>(),
+                   cur_stream());
+  return {rec, (int64_t)pa};
+}
+
+// records of every rank in rank order -> {vec [4, C], count int64 [1]} + running-stat update
+std::vector<at::Tensor> syncbn_merge_impl(const char* fn, const at::Tensor& recs,
+                                          const OptTensor& gamma, const OptTensor& beta,
+                                          const OptTensor& running_mean,
+                                          const OptTensor& running_var, double momentum,
+                                          double eps) {
+  int64_t C;
+  const int N = check_records(fn, recs, recs, &C);
+  float *rm, *rv;
+  running_ptrs(fn, running_mean, running_var, recs, C, &rm, &rv);
+  const float* gp = vec_ptr_opt(fn, "weight", gamma, recs, C);
+  const float* bp = vec_ptr_opt(fn, "bias", beta, recs, C);
+  c10::DeviceGuard guard(recs.device());
+  at::Tensor vec = at::empty({4, C}, recs.options().dtype(at::kFloat));
+  at::Tensor count = at::empty({1}, recs.options().dtype(at::kLong));
+  mv_syncbn_merge(recs.data_ptr<int32_t>(), N, (int)C, rm, rv, gp, bp, (float)momentum,
+                  (float)eps, vec.data_ptr<float>(), count.data_ptr<int64_t>(), cur_stream());
+  return {vec, count};
+}
+
+// merge + apply: {y, vec, count} or (want_mask: relu + residual only) {y, vec, count, mask}
+std::vector<at::Tensor> syncbn_fwd(at::Tensor x, at::Tensor recs, c10::optional<at::Tensor> gamma,
+                                   c10::optional<at::Tensor> beta,
+                                   c10::optional<at::Tensor> running_mean,
+                                   c10::optional<at::Tensor> running_var, double momentum,
+                                   double eps, bool relu, c10::optional<at::Tensor> residual,
+                                   bool want_mask) {
+  const char* fn = "syncbn_fwd";
+  int64_t C, CR;
+  const int64_t M = check_act(fn, "x", x, x, &C);
+  TORCH_CHECK(M > 0, fn, ": empty input");
+  check_records(fn, recs, x, &CR);
+  TORCH_CHECK(CR == C, fn, ": records are for ", CR, " channels, x has ", C);
+  const void* rp = opt_same(fn, "residual", residual, x);
+  TORCH_CHECK(!want_mask || (relu && rp), fn, ": the output bitmask needs relu and a residual");
+  std::vector<at::Tensor> out =
+      syncbn_merge_impl(fn, recs, gamma, beta, running_mean, running_var, momentum, eps);
+  c10::DeviceGuard guard(x.device());
+  const float* vp = out[0].data_ptr<float>();
+  at::Tensor y = at::empty_like(x);
+  at::Tensor mask;
+  if (want_mask) mask = at::empty({M, C / 8}, x.options().dtype(at::kByte));
+  mv_bn_apply(x.data_ptr(), rp, y.data_ptr(), M, (int)C, vp + 2 * C, vp + 3 * C, relu,
+              cur_stream(), want_mask ? mask.data_ptr() : nullptr);
+  if (want_mask) return {y, out[0], out[1], mask};
+  return {y, out[0], out[1]};
+}
+
+// The backward's local half, {tot [2, C], dgamma, dbeta, dz}: the reduce pass of bn_bwd's
+// modes, this rank's affine gradients and its (sum dz, sum dz (x - mean)) for the sum over
+// ranks; dz defined for modes 2 and 3
+std::vector<at::Tensor> syncbn_bwd_reduce(int64_t mode, at::Tensor dy, at::Tensor x,
+                                          c10::optional<at::Tensor> y, at::Tensor vec,
+                                          bool need_affine_grad) {
+  const char* fn = "syncbn_bwd_reduce";
+  int64_t C, C2;
+  check_act(fn, "dy", dy, dy, &C2);
+  const int64_t M = check_act(fn, "x", x, dy, &C);
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), fn,
+              ": dy must match x in shape and layout");
+  TORCH_CHECK(M > 0, fn, ": empty input");
+  TORCH_CHECK(mode >= 0 && mode <= 3, fn, ": bad mode");
+  const float* vp = vec_ptr(fn, "vec", vec, x, 4 * C);
+  const void* yp = nullptr;
+  if (mode == 2) {
+    yp = opt_same(fn, "y", y, x);
+    TORCH_CHECK(yp, fn, ": mode 2 needs the saved output");
+  } else if (mode == 3) {
+    TORCH_CHECK(given(y), fn, ": mode 3 needs the forward's [M, C/8] uint8 bitmask");
+    yp = vec_ptr<uint8_t>(fn, "y", *y, x, M * (C / 8));
+  }
+  c10::DeviceGuard guard(x.device());
+  auto fo = x.options().dtype(at::kFloat);
+  const int P = mv_bn_partials(M, (int)C);
+  at::Tensor partial = at::empty({(int64_t)P * 2 * C}, fo);
+  at::Tensor tot = at::empty({2, C}, fo);
+  at::Tensor dg, db, dz;
+  if (need_affine_grad) {
+    dg = at::empty({C}, fo);
+    db = at::empty({C}, fo);
+  }
+  if (mode >= 2) dz = at::empty_like(x);
+  const int pa = mv_bn_bwd_reduce_pass((int)mode, dy.data_ptr(), nullptr, x.data_ptr(), yp,
+                                       mode >= 2 ? dz.data_ptr() : nullptr, M, (int)C, vp,
+                                       vp + 2 * C, vp + 3 * C, partial.data_ptr<float>(), P, 1, 1,
+                                       1, cur_stream());
+  mv_syncbn_bwd_local(partial.data_ptr<float>(), pa, (int)C, vp + C,
+                      need_affine_grad ? dg.data_ptr<float>() : nullptr,
+                      need_affine_grad ? db.data_ptr<float>() : nullptr, tot.data_ptr<float>(),
+                      cur_stream());
+  return {tot, dg, db, dz};
+}
+
+// The backward's global half: dx from the totals summed over ranks and the forward's global
+// count; d = dy (modes 0, 1) or the reduce's dz (modes 2, 3)
+at::Tensor syncbn_bwd_dx(int64_t mode, at::Tensor d, at::Tensor x, at::Tensor vec,
+                         c10::optional<at::Tensor> gamma, at::Tensor tot, at::Tensor count) {
+  const char* fn = "syncbn_bwd_dx";
+  int64_t C, C2;
+  check_act(fn, "d", d, d, &C2);
+  const int64_t M = check_act(fn, "x", x, d, &C);
+  TORCH_CHECK(d.sizes() == x.sizes() && d.strides() == x.strides(), fn,
+              ": d must match x in shape and layout");
+  TORCH_CHECK(mode >= 0 && mode <= 3, fn, ": bad mode");
+  const float* vp = vec_ptr(fn, "vec", vec, x, 4 * C);
+  const float* gp = vec_ptr_opt(fn, "weight", gamma, x, C);
+  const float* tp = vec_ptr(fn, "tot", tot, x, 2 * C);
+  const int64_t* cp = vec_ptr<int64_t>(fn, "count", count, x, 1);
+  c10::DeviceGuard guard(x.device());
+  at::Tensor co = at::empty({3, C}, x.options().dtype(at::kFloat));
+  at::Tensor dx = at::empty_like(x);
+  mv_syncbn_bwd_coeffs(tp, cp, (int)C, vp, vp + C, gp, co[0].data_ptr<float>(),
+                       co[1].data_ptr<float>(), co[2].data_ptr<float>(), cur_stream());
+  mv_bn_bwd_dx_pass((int)mode, d.data_ptr(), x.data_ptr(), dx.data_ptr(), M, (int)C, vp + 2 * C,
+                    vp + 3 * C, co[0].data_ptr<float>(), co[1].data_ptr<float>(),
+                    co[2].data_ptr<float>(), cur_stream());
+  return dx;
+}
+
+// ---------------------------------------------------------------------------
 // NHWC pooling
 // ---------------------------------------------------------------------------
 std::vector<at::Tensor> maxpool_fwd(at::Tensor x, c10::optional<at::Tensor> scale,
@@ -523,6 +675,25 @@ void bind_bn(pybind11::module_& m) {
         "BN backward finalize only: [5, C] = (dgamma, dbeta, ca, cb, cc) from partials");
   m.def("bn_bwd_from_partials", &bn_bwd_from_partials,
         "BN backward finalize + dx from GEMM-epilogue partials -> (dx, dgamma, dbeta)");
+  // SyncBatchNorm has a namespace of its own: mivod._mvk._syncbn
+  pybind11::module_ sb = m.def_submodule(
+      "_syncbn", "SyncBatchNorm: the local BN passes and the kernels around its two collectives");
+  sb.def("syncbn_stats", &syncbn_stats,
+        "{record int32 [3C + 4], P}: local statistics pass + this rank's SyncBatchNorm record",
+        pybind11::arg("x"), pybind11::arg("shift") = pybind11::none());
+  sb.def("syncbn_merge",
+        [](at::Tensor recs, Opt gamma, Opt beta, Opt running_mean, Opt running_var, double momentum,
+           double eps) {
+          return syncbn_merge_impl("syncbn_merge", recs, gamma, beta, running_mean, running_var,
+                                   momentum, eps);
+        },
+        "gathered [N, 3C + 4] records -> {vec [4, C], count int64 [1]} + running-stat update");
+  sb.def("syncbn_fwd", &syncbn_fwd,
+        "SyncBatchNorm forward after the allgather: merge + apply -> {y, vec, count[, mask]}");
+  sb.def("syncbn_bwd_reduce", &syncbn_bwd_reduce,
+        "SyncBatchNorm backward, local half -> {tot [2, C], dgamma, dbeta, dz}");
+  sb.def("syncbn_bwd_dx", &syncbn_bwd_dx,
+        "SyncBatchNorm backward, global half: dx from the summed totals and the global count");
   m.def("maxpool_fwd", &maxpool_fwd, "NHWC maxpool with fused affine+ReLU prologue -> (y, idx)");
   m.def("maxpool_bwd", &maxpool_bwd, "NHWC maxpool backward (gather, + second grad stream)");
   m.def("maxpool_bn_bwd", &maxpool_bn_bwd,

@@ -51,3 +51,17 @@ int mv_bn_apply_colsum(const void* x, void* y, int64_t M, int C, const float* sc
 void mv_bn_stats_strided(const void* x, int Nb, int H, int W, int C, int ds, float* partial,
                          int P, float* save_mean, float* save_invstd, float* scale, float* bias,
                          hipStream_t st);
+
+// Single passes of the above, for callers that put their own finalize between them
+// (mv_syncbn.h: statistics and gradient sums that cross ranks before they are finalized).
+// Each reduce returns the number of [2][C] partial rows it wrote (<= P).
+int mv_bn_stats_pass(const void* x, int64_t M, int C, const float* shift, float* partial, int P,
+                     hipStream_t st);
+int mv_bn_bwd_reduce_pass(int mode, const void* dy, const void* dy2, const void* x, const void* y,
+                          void* dz, int64_t M, int C, const float* save_mean, const float* scale,
+                          const float* bias, float* partial, int P, int dy2_stride, int H, int W,
+                          hipStream_t st);
+// dx = ca * d + cb * x + cc with d = dy (mode 0), relu'(x) dy (mode 1) or dz (modes 2, 3)
+void mv_bn_bwd_dx_pass(int mode, const void* d, const void* x, void* dx, int64_t M, int C,
+                       const float* scale, const float* bias, const float* ca, const float* cb,
+                       const float* cc, hipStream_t st);

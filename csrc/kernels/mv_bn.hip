@@ -18,6 +18,7 @@
 // cancellation in E[x^2] - E[x]^2.
 #include "mv_common.h"
 #include "mv_bn.h"
+#include "mv_bn_fin.h"
 
 #include <cstdlib>
 #include <mutex>
@@ -28,8 +29,6 @@ namespace bn {
 
 constexpr int kCB = 256;    // channels per workgroup slab
 constexpr int kTPR = kCB / kVec;  // 32 lanes per row (when C >= 256)
-constexpr int kFinCh = 2;   // finalize: channels per workgroup
-constexpr int kFinSub = kBlock / kFinCh;  // 128 partial-subsets per channel
 
 struct Geo {
   int64_t M;
@@ -166,56 +165,6 @@ __global__ __launch_bounds__(kBlock) void stats_kernel(const __bf16* __restrict_
     float s = 0.f;
     for (int t = 0; t < g.RPI; ++t) s += red[k][t * g.TPR * kVec + cc];
     partial[((int64_t)blockIdx.x * 2 + k) * g.C + blockIdx.y * g.CB + cc] = s;
-  }
-}
-
-// Fixed-order reduction of [P][2][C] partials for kFinCh channels per block.
-__device__ __forceinline__ void fin_reduce(const float* __restrict__ partial, int P, int C, int ch,
-                                           float* o1, float* o2) {
-  const int lc = threadIdx.x % kFinCh, sub = threadIdx.x / kFinCh;
-  // 4 independent accumulator pairs keep 8 loads in flight per lane; the
-  // combination order is fixed, so the result is deterministic.
-  float a0 = 0.f, b0 = 0.f, a1 = 0.f, b1 = 0.f, a2 = 0.f, b2 = 0.f, a3 = 0.f, b3 = 0.f;
-  if (ch < C) {
-    const int64_t st = (int64_t)2 * C;
-    const float* q = partial + ch;
-    int p = sub;
-    for (; p + 3 * kFinSub < P; p += 4 * kFinSub) {
-      a0 += q[(int64_t)p * st];
-      b0 += q[(int64_t)p * st + C];
-      a1 += q[(int64_t)(p + kFinSub) * st];
-      b1 += q[(int64_t)(p + kFinSub) * st + C];
-      a2 += q[(int64_t)(p + 2 * kFinSub) * st];
-      b2 += q[(int64_t)(p + 2 * kFinSub) * st + C];
-      a3 += q[(int64_t)(p + 3 * kFinSub) * st];
-      b3 += q[(int64_t)(p + 3 * kFinSub) * st + C];
-    }
-    for (; p < P; p += kFinSub) {
-      a0 += q[(int64_t)p * st];
-      b0 += q[(int64_t)p * st + C];
-    }
-  }
-  float a = (a0 + a1) + (a2 + a3), b = (b0 + b1) + (b2 + b3);
-  // fixed xor-tree across the 32 lanes of a wave that share this channel
-  // (lane = sub*kFinCh + lc), then 4 wave partials combined in order via LDS
-#pragma unroll
-  for (int o = kFinCh; o < kWave; o <<= 1) {
-    a += __shfl_xor(a, o, kWave);
-    b += __shfl_xor(b, o, kWave);
-  }
-  __shared__ float red[2][kBlock / kWave][kFinCh];
-  const int w = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  if (lane < kFinCh) {
-    red[0][w][lane] = a;
-    red[1][w][lane] = b;
-  }
-  __syncthreads();
-  if (sub == 0) {
-    float x = 0.f, y = 0.f;
-#pragma unroll
-    for (int k = 0; k < kBlock / kWave; ++k) { x += red[0][k][lc]; y += red[1][k][lc]; }
-    *o1 = x;
-    *o2 = y;
   }
 }
 
@@ -805,6 +754,41 @@ void mv_bn_bwd(int mode, const void* dy, const void* dy2, const void* x, const v
     case 1: launch_bwd_dx<1>(dyp, xp, scale, bias, ca, cb, cc, dxp, M, C, st); break;
     default: launch_bwd_dx<0>((const __bf16*)dzp, xp, scale, bias, ca, cb, cc, dxp, M, C, st); break;
   }
+}
+
+int mv_bn_stats_pass(const void* x, int64_t M, int C, const float* shift, float* partial, int P,
+                     hipStream_t st) {
+  Geo gr = reduce_geo(M, C, P, (const void*)&stats_kernel<8, true>);
+  const dim3 grr = grid_of(gr);
+  hipLaunchKernelGGL((stats_kernel<8, true>), grr, dim3(kBlock), 0, st, (const __bf16*)x, shift,
+                     partial, gr);
+  return (int)grr.x;
+}
+
+int mv_bn_bwd_reduce_pass(int mode, const void* dy, const void* dy2, const void* x, const void* y,
+                          void* dz, int64_t M, int C, const float* save_mean, const float* scale,
+                          const float* bias, float* partial, int P, int dy2_stride, int H, int W,
+                          hipStream_t st) {
+  const __bf16* dyp = (const __bf16*)dy;
+  const __bf16* dy2p = (const __bf16*)dy2;
+  const __bf16* xp = (const __bf16*)x;
+  const __bf16* yp = (const __bf16*)y;
+  __bf16* dzp = (__bf16*)dz;
+  switch (mode) {
+    case 0: return launch_bwd_reduce<0>(dyp, dy2p, xp, yp, save_mean, scale, bias, dzp, partial, P, M, C, dy2_stride, H, W, st);
+    case 1: return launch_bwd_reduce<1>(dyp, dy2p, xp, yp, save_mean, scale, bias, dzp, partial, P, M, C, dy2_stride, H, W, st);
+    case 2: return launch_bwd_reduce<2>(dyp, dy2p, xp, yp, save_mean, scale, bias, dzp, partial, P, M, C, dy2_stride, H, W, st);
+    default: return launch_bwd_reduce<3>(dyp, dy2p, xp, yp, save_mean, scale, bias, dzp, partial, P, M, C, dy2_stride, H, W, st);
+  }
+}
+
+void mv_bn_bwd_dx_pass(int mode, const void* d, const void* x, void* dx, int64_t M, int C,
+                       const float* scale, const float* bias, const float* ca, const float* cb,
+                       const float* cc, hipStream_t st) {
+  if (mode == 1)
+    launch_bwd_dx<1>((const __bf16*)d, (const __bf16*)x, scale, bias, ca, cb, cc, (__bf16*)dx, M, C, st);
+  else
+    launch_bwd_dx<0>((const __bf16*)d, (const __bf16*)x, scale, bias, ca, cb, cc, (__bf16*)dx, M, C, st);
 }
 
 // BN backward whose reduce pass ran inside the producing data-gradient GEMM

@@ -405,6 +405,172 @@ class BatchNorm2d(nn.BatchNorm2d):
         super()._load_from_state_dict(*args, **kwargs)
 
 
+# ------------------------------------------------------------------ SyncBatchNorm
+# Batch statistics over every rank's rows (hvd.SyncBatchNorm, mivod/torch/sync_batch_norm.py).
+# The streaming passes are the local BN's; between them each direction has one small
+# collective (csrc/kernels/mv_syncbn.hip): an allgather of fixed-size statistics records
+# in the forward, a sum of the [2, C] gradient totals in the backward.  dgamma / dbeta stay
+# local sums, as horovod's: the optimizer's allreduce averages them like any gradient.
+def _sync_gpu_transport():
+    """The transport the fast path's collectives ride: None at world size 1, unless
+    MIVOD_FORCE_COLLECTIVES=1 built a 1-rank communicator."""
+    from ..common import basics
+    return basics.state().gpu
+
+
+class _SyncBNActTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, residual):
+        from ..parallel.order import ORDER
+        nat = K.native()._syncbn
+        mode = 2 if (relu and residual is not None) else (1 if relu else 0)
+        rec, _ = nat.syncbn_stats(x, running_mean)
+        tr = _sync_gpu_transport()
+        if tr is not None:
+            recs = torch.empty((tr.size, rec.numel()), dtype=rec.dtype, device=rec.device)
+            with ORDER.issue():
+                tr.allgather_into(recs.view(-1), rec)
+        else:
+            recs = rec.unsqueeze(0)
+        if mode == 2 and _BN_MASK:
+            y, vec, count, keep = nat.syncbn_fwd(x, recs, weight, bias, running_mean, running_var,
+                                                 momentum, eps, True, residual, True)
+            mode = 3
+        else:
+            y, vec, count = nat.syncbn_fwd(x, recs, weight, bias, running_mean, running_var,
+                                           momentum, eps, relu, residual, False)
+            keep = y if mode == 2 else None
+        ctx.mode = mode
+        ctx.has_res = residual is not None
+        ctx.save_for_backward(x, keep, vec, weight, count)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from ..parallel import transport as T
+        from ..parallel.order import ORDER
+        nat = K.native()._syncbn
+        x, keep, vec, weight, count = ctx.saved_tensors
+        need_affine = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dy = _cl(dy)
+        tot, dg, db, dz = nat.syncbn_bwd_reduce(ctx.mode, dy, x, keep, vec, need_affine)
+        # every rank takes part, whether or not it wants dx itself
+        tr = _sync_gpu_transport()
+        if tr is not None:
+            with ORDER.issue():
+                tr.allreduce_(tot.view(-1), T.SUM)
+        d = dz if ctx.mode >= 2 else dy
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = nat.syncbn_bwd_dx(ctx.mode, d, x, vec, weight, tot, count)
+        return (dx, dg if ctx.needs_input_grad[1] else None,
+                db if ctx.needs_input_grad[2] else None, None, None, None, None, None,
+                d if (ctx.has_res and ctx.needs_input_grad[8]) else None)
+
+
+def _chan_merge(recs, c):
+    """Rank-ordered Chan merge of [N, 2 c + 1] float64 rows (mean, M2, count) -> fp32 mean,
+    fp32 M2 and the float64 total count.  A zero-row rank has weight 0."""
+    tot = recs.new_zeros(())
+    mean = recs.new_zeros(c, dtype=torch.float32)
+    m2 = recs.new_zeros(c, dtype=torch.float32)
+    for r in range(recs.shape[0]):
+        nr = recs[r, -1]
+        nt = tot + nr
+        w = (nr / nt.clamp(min=1.0)).float()
+        d = recs[r, :c].float() - mean
+        mean = mean + d * w
+        m2 = m2 + recs[r, c:2 * c].float() + d * d * (tot.float() * w)
+        tot = nt
+    return mean, m2, tot
+
+
+class _SyncBNRef(torch.autograd.Function):
+    """The same mathematics in plain torch (fp32 statistics) over
+    ``mivod.parallel.collectives``, for every input the fused path does not take: CPU
+    tensors, fp32 / NCHW, 2-D, 3-D and 5-D input."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, residual):
+        from ..parallel import collectives as C
+        c = x.shape[1]
+        dims = [0] + list(range(2, x.dim()))
+        shape = [1, c] + [1] * (x.dim() - 2)
+        n = x.numel() // c
+        xf = x.float()
+        if n > 0:
+            mean_l = xf.mean(dims)
+            m2_l = (xf - mean_l.view(shape)).square().sum(dims)
+        else:
+            mean_l = m2_l = xf.new_zeros(c)
+        rec = torch.cat((mean_l.double(), m2_l.double(),
+                         torch.full((1,), float(n), dtype=torch.float64, device=x.device)))
+        mean, m2, tot = _chan_merge(C.allgather(rec.unsqueeze(0)), c)
+        var = m2 / tot.clamp(min=1.0).float()
+        invstd = torch.rsqrt(var + eps)
+        if running_mean is not None:
+            unb = m2 / (tot - 1.0).clamp(min=1.0).float()
+            running_mean.mul_(1.0 - momentum).add_(mean.to(running_mean.dtype), alpha=momentum)
+            running_var.mul_(1.0 - momentum).add_(unb.to(running_var.dtype), alpha=momentum)
+        scale = invstd * (weight.float() if weight is not None else 1.0)
+        shift = (bias.float() if bias is not None else 0.0) - mean * scale
+        y = xf * scale.view(shape) + shift.view(shape)
+        if residual is not None:
+            y = y + residual.float()
+        if relu:
+            y = F.relu(y)
+        ctx.relu, ctx.shape, ctx.dims = relu, shape, dims
+        ctx.res_dtype = residual.dtype if residual is not None else None
+        ctx.save_for_backward(x, weight, mean, invstd, tot, (y > 0) if relu else None)
+        return y.to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from ..parallel import collectives as C
+        x, weight, mean, invstd, tot, pos = ctx.saved_tensors
+        shape, dims = ctx.shape, ctx.dims
+        dz = dy.float()
+        if ctx.relu:
+            dz = dz * pos
+        xc = x.float() - mean.view(shape)
+        sums = torch.stack((dz.sum(dims), (dz * xc).sum(dims)))
+        dg = (sums[1] * invstd).to(weight.dtype) if weight is not None else None
+        db = sums[0].clone().to(weight.dtype) if weight is not None else None
+        sums = C.allreduce_(sums, C.Sum)      # in place: dg / db above are this rank's own
+        dx = None
+        if ctx.needs_input_grad[0]:
+            inv_m = (1.0 / tot.clamp(min=1.0)).float()
+            a = invstd * (weight.float() if weight is not None else 1.0)
+            b = -a * invstd * invstd * sums[1] * inv_m
+            dx = (a.view(shape) * dz + b.view(shape) * xc
+                  - (a * sums[0] * inv_m).view(shape)).to(x.dtype)
+        dres = dz.to(ctx.res_dtype) if (ctx.res_dtype is not None and
+                                         ctx.needs_input_grad[8]) else None
+        return (dx, dg if ctx.needs_input_grad[1] else None,
+                db if ctx.needs_input_grad[2] else None, None, None, None, None, None, dres)
+
+
+def sync_batch_norm_act(x, weight, bias, running_mean, running_var, training, momentum, eps,
+                        relu=False, residual=None):
+    """``act(batch_norm(x) + residual)`` with the batch statistics of ALL ranks' rows (ranks
+    may hold different batch sizes).  Evaluation uses the running statistics through the
+    local path.  Fused bf16 NHWC inputs run the HIP path with one collective per direction;
+    anything else the plain-torch path with the same mathematics."""
+    if not training:
+        return batch_norm_act(x, weight, bias, running_mean, running_var, False, momentum, eps,
+                              relu, residual)
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("sync_batch_norm_act: residual must have x's shape")
+    if x.numel() > 0 and _fusable(x, weight) and (residual is None or
+                                                  residual.dtype == torch.bfloat16):
+        if residual is not None:
+            residual = _cl(residual)
+        return _SyncBNActTrain.apply(x, weight, bias, running_mean, running_var, float(momentum),
+                                     float(eps), bool(relu), residual)
+    return _SyncBNRef.apply(x, weight, bias, running_mean, running_var, float(momentum),
+                            float(eps), bool(relu), residual)
+
+
 # ------------------------------------------------------------------ pooling
 class _BNReluMaxPool(torch.autograd.Function):
     """maxpool(relu(bn(x))) for the ResNet stem: statistics pass, then ONE

@@ -1,6 +1,8 @@
 """``import mivod.torch as hvd`` — horovod.torch-compatible API on PyTorch-ROCm.
 
-Parity: horovod 0.18.1 ``horovod/torch``.
+Parity: horovod 0.18.1 ``horovod/torch``, plus
+``SyncBatchNorm`` from later horovod releases (``sync_batch_norm.py``: cross-rank batch
+statistics on the fused BN kernels; not yet wired into the ResNet conv+BN folds).
 """
 from ..common.basics import (comm_stream, cross_rank, cross_size, device, gloo_enabled, init, is_initialized,
                              local_rank, local_size, mpi_enabled, mpi_threads_supported,
@@ -14,3 +16,4 @@ from .mpi_ops import (Adasum, Average, HorovodInternalError, Sum, allgather, all
                       join, poll, synchronize)
 from .optimizer import DistributedOptimizer
 from .graphs import GraphedStep, make_graphed_step
+from .sync_batch_norm import SyncBatchNorm
