@@ -76,7 +76,7 @@ void nonfinite_scan(at::Tensor x, at::Tensor flag) {
 
 // The flat SGD / Adam / Adadelta kernels move 8 elements per lane with 16-byte accesses and
 // have no scalar fallback (the arenas hand them 64-element-aligned slices), so an offset
-// view is an error here; LARS guards its vector body itself and takes any offset.
+// view is an error here; LARS and LAMB guard their vector bodies themselves and take any offset.
 void check_aligned16(const char* fn, const char* what, const void* p) {
   TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 15u) == 0, fn, ": ", what,
               " must be 16-byte aligned");
@@ -189,6 +189,28 @@ void lars_step(at::Tensor g, at::Tensor w, at::Tensor mom, c10::optional<at::Ten
                  s.dyn, s.skip, cur_stream());
 }
 
+void lamb_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
+               c10::optional<at::Tensor> model, at::Tensor cbeg, at::Tensor clen, at::Tensor cseg,
+               at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor sflag, at::Tensor partial,
+               at::Tensor norms, double lr, double b1, double b2, double eps, double wd,
+               double gscale, int64_t step, c10::optional<at::Tensor> dyn,
+               c10::optional<at::Tensor> skip) {
+  const StepArgs s = step_args("lamb_step", g, w, model, dyn, skip, false);
+  float* mp = vec_ptr("lamb_step", "exp_avg", m, g, g.numel());
+  float* vp = vec_ptr("lamb_step", "exp_avg_sq", v, g, g.numel());
+  ChunkTable ct = make_table("lamb_step", g, cbeg, clen, cseg, seg_c0, seg_nc);
+  int32_t* fp = vec_ptr<int32_t>("lamb_step", "sflag", sflag, g, ct.nseg, true);
+  float* pp = vec_ptr("lamb_step", "partial", partial, g, 2 * (int64_t)ct.nchunks, true);
+  float* np = vec_ptr("lamb_step", "norms", norms, g, 2 * (int64_t)ct.nseg, true);
+  TORCH_CHECK(step >= 1, "lamb_step: step must be >= 1");
+  const double bc1 = 1.0 - std::pow(b1, (double)step);
+  const double bc2 = 1.0 - std::pow(b2, (double)step);
+  c10::DeviceGuard guard(g.device());
+  mv_launch_lamb(g.data_ptr(), dtype_code(g), s.w, mp, vp, s.model, s.model_dt, ct, fp, pp, np,
+                 (float)lr, b1, b2, (float)eps, (float)wd, (float)gscale, (float)bc1, (float)bc2,
+                 s.dyn, s.skip, cur_stream());
+}
+
 void seg_dot3(at::Tensor a, at::Tensor b, at::Tensor cbeg, at::Tensor clen, at::Tensor cseg,
               at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor partial, at::Tensor out,
               bool swap) {
@@ -271,6 +293,10 @@ void bind_optim(pybind11::module_& m) {
   m.def("adam_step", &adam_step, "fused flat Adam/AdamW step");
   m.def("adadelta_step", &adadelta_step, "fused flat Adadelta step");
   m.def("lars_step", &lars_step, "fused segmented LARS step");
+  // LAMB has a namespace of its own: mivod._mvk._lamb
+  pybind11::module_ lb = m.def_submodule(
+      "_lamb", "LAMB: Adam moments with a per-segment trust ratio on the flat-arena path");
+  lb.def("lamb_step", &lamb_step, "fused segmented LAMB step");
   m.def("seg_dot3", &seg_dot3, "per-segment (a.b, |a|^2, |b|^2) (swap: (a.b, |b|^2, |a|^2))");
   m.def("adasum_merge", &adasum_merge,
         "one vector-halving Adasum level: merge with fixed-order group Gram sums + fused wire cast");

@@ -49,6 +49,14 @@ void mv_launch_lars(const void* g, int gd, float* w, float* mom, void* model, in
                     const ChunkTable& ct, const int32_t* sflag, float* partial, float* norms,
                     float lr, float momentum, float wd, float eta, float gscale, float eps,
                     int first, const float* dyn, const int* skip, hipStream_t st);
+// LAMB: m, v updated and per-chunk (|w|^2, |u|^2) partials, the segment reduce into
+// norms[2 * nseg], then w -= lr * trust * u with u recomputed from the stored m, v and w.
+// sflag bit0: the segment takes no weight decay and trust 1.  dyn overrides lr, bc1, bc2;
+// skip makes both streaming kernels return before they touch w, m, v or the model copy.
+void mv_launch_lamb(const void* g, int gd, float* w, float* m, float* v, void* model, int md,
+                    const ChunkTable& ct, const int32_t* sflag, float* partial, float* norms,
+                    float lr, double b1, double b2, float eps, float wd, float gscale, float bc1,
+                    float bc2, const float* dyn, const int* skip, hipStream_t st);
 // swap: store (a.b, |b|^2, |a|^2) (the Adasum level kernels, f holding b)
 void mv_launch_seg_dot3(const void* a, const void* b, int dt, const ChunkTable& ct, float* partial,
                         float* out, int swap, hipStream_t st);

@@ -6,7 +6,7 @@
 //   K1/K2  mv_mt_copy        multi-tensor fusion-buffer pack / unpack, fused cast
 //                            (fp32/bf16/fp16 compression) and pre/post scale
 //   K4/K5  mv_flat_cast      flat compress / decompress / scale of a bucket
-//   K6     mv_{sgd,adam,adadelta}_flat, mv_lars_*  fused optimizer steps that
+//   K6     mv_{sgd,adam,adadelta}_flat, mv_lars_*, mv_lamb_*  fused optimizer steps that
 //                            run directly on a reduced flat gradient bucket,
 //                            fp32 master weights + bf16 model copy written in
 //                            the same pass (grad read once)
@@ -511,6 +511,140 @@ __global__ __launch_bounds__(kBlock) void lars_flat_kernel(const TG* __restrict_
   }
 }
 
+// LAMB (You et al. 2019): Adam moments, then per segment w -= lr * (|w| / |u|) * u with
+// u = m_hat / (sqrt(v_hat) + eps) + wd * w.  Two streaming kernels over the chunk table with
+// seg_reduce_kernel<2> between them; segments flagged (bit0) take wd = 0 and trust 1, as in
+// lars_flat_kernel.  Bias correction is always on.
+struct LambHp { float lr, b1, b2, omb1, omb2, eps, wd, gscale, bc1, bc2; };
+
+// The update direction of one element from the UPDATED moments and the master BEFORE its
+// update; rbc1 = 1 / bc1, rbc2 = 1 / sqrt(bc2).  Stage 1 measures |u| and stage 2 applies u
+// recomputed from the stored m and v, so both go through this one expression; the two
+// fused multiply-adds are spelled out so that neither call site can be contracted
+// differently from the other: the norm that was measured is the norm of what is applied.
+__device__ __forceinline__ float lamb_u(float m, float v, float w, float rbc1, float rbc2,
+                                        float eps, float wd) {
+  const float den = __builtin_fmaf(sqrtf(v), rbc2, eps);
+  return __builtin_fmaf(wd, w, m * rbc1 / den);
+}
+
+// Stage 1: m and v in place, one (sum w^2, sum u^2) partial per chunk in fixed order.
+template <typename TG>
+__global__ __launch_bounds__(kBlock) void lamb_moments_kernel(const TG* __restrict__ g,
+                                                               const float* __restrict__ w,
+                                                               float* __restrict__ m,
+                                                               float* __restrict__ v,
+                                                               const int64_t* __restrict__ cbeg,
+                                                               const int32_t* __restrict__ clen,
+                                                               const int32_t* __restrict__ cseg,
+                                                               const int32_t* __restrict__ sflag,
+                                                               float* __restrict__ partial,
+                                                               LambHp hp,
+                                                               const float* __restrict__ dyn,
+                                                               const int* __restrict__ skip) {
+  if (skip && *skip) return;   // uniform: no lane reaches block_sum's barrier
+  if (dyn) { hp.bc1 = dyn[2]; hp.bc2 = dyn[3]; }
+  const int c = blockIdx.x;
+  const int64_t beg = cbeg[c];
+  const int len = clen[c];
+  const float wd = (sflag[cseg[c]] & 1) ? 0.f : hp.wd;
+  const float rbc1 = 1.f / hp.bc1;
+  const float rbc2 = 1.f / sqrtf(hp.bc2);
+  float acc[2] = {0.f, 0.f};
+  // the same body layout as lars_flat_kernel: vector prefix where every operand is
+  // 16-byte aligned, scalar tail (all of the chunk at an unaligned offset)
+  const int nvec = (aligned16(g + beg) && aligned16(w + beg) && aligned16(m + beg) &&
+                    aligned16(v + beg)) ? (len / kVec) * kVec : 0;
+  for (int i = threadIdx.x * kVec; i < nvec; i += kBlock * kVec) {
+    const int64_t k = beg + i;
+    float gv[8], wv[8], mv_[8], vv[8];
+    load8(g + k, gv);
+    load8(w + k, wv);
+    load8(m + k, mv_);
+    load8(v + k, vv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float gr = gv[j] * hp.gscale;
+      mv_[j] = hp.b1 * mv_[j] + hp.omb1 * gr;
+      vv[j] = hp.b2 * vv[j] + hp.omb2 * gr * gr;
+      const float u = lamb_u(mv_[j], vv[j], wv[j], rbc1, rbc2, hp.eps, wd);
+      acc[0] += wv[j] * wv[j];
+      acc[1] += u * u;
+    }
+    store8(m + k, mv_);
+    store8(v + k, vv);
+  }
+  for (int i = nvec + threadIdx.x; i < len; i += kBlock) {
+    const int64_t k = beg + i;
+    const float wk = w[k];
+    const float gr = ld1(g + k) * hp.gscale;
+    const float mk = hp.b1 * m[k] + hp.omb1 * gr;
+    const float vk = hp.b2 * v[k] + hp.omb2 * gr * gr;
+    m[k] = mk;
+    v[k] = vk;
+    const float u = lamb_u(mk, vk, wk, rbc1, rbc2, hp.eps, wd);
+    acc[0] += wk * wk;
+    acc[1] += u * u;
+  }
+  block_sum<2>(acc);
+  if (threadIdx.x == 0) {
+    partial[2 * (int64_t)c] = acc[0];
+    partial[2 * (int64_t)c + 1] = acc[1];
+  }
+}
+
+// Stage 2: trust from the segment's norms, w -= lr * trust * u, the model copy.
+template <typename TP>
+__global__ __launch_bounds__(kBlock) void lamb_apply_kernel(float* __restrict__ w,
+                                                             const float* __restrict__ m,
+                                                             const float* __restrict__ v,
+                                                             TP* __restrict__ model,
+                                                             const int64_t* __restrict__ cbeg,
+                                                             const int32_t* __restrict__ clen,
+                                                             const int32_t* __restrict__ cseg,
+                                                             const int32_t* __restrict__ sflag,
+                                                             const float* __restrict__ norms,
+                                                             LambHp hp,
+                                                             const float* __restrict__ dyn,
+                                                             const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  if (dyn) { hp.lr = dyn[0]; hp.bc1 = dyn[2]; hp.bc2 = dyn[3]; }
+  const int c = blockIdx.x;
+  const int64_t beg = cbeg[c];
+  const int len = clen[c];
+  const int s = cseg[c];
+  const bool plain = sflag[s] & 1;
+  const float wd = plain ? 0.f : hp.wd;
+  const float wn = sqrtf(norms[2 * s]);
+  const float un = sqrtf(norms[2 * s + 1]);
+  float trust = 1.f;
+  if (!plain && wn > 0.f && un > 0.f) trust = wn / un;
+  const float slr = hp.lr * trust;
+  const float rbc1 = 1.f / hp.bc1;
+  const float rbc2 = 1.f / sqrtf(hp.bc2);
+  const int nvec = (aligned16(w + beg) && aligned16(m + beg) && aligned16(v + beg) &&
+                    (!model || aligned16(model + beg))) ? (len / kVec) * kVec : 0;
+  for (int i = threadIdx.x * kVec; i < nvec; i += kBlock * kVec) {
+    const int64_t k = beg + i;
+    float wv[8], mv_[8], vv[8];
+    load8(w + k, wv);
+    load8(m + k, mv_);
+    load8(v + k, vv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      wv[j] -= slr * lamb_u(mv_[j], vv[j], wv[j], rbc1, rbc2, hp.eps, wd);
+    store8(w + k, wv);
+    if (model) store_model(model + k, wv);
+  }
+  for (int i = nvec + threadIdx.x; i < len; i += kBlock) {
+    const int64_t k = beg + i;
+    float wk = w[k];
+    wk -= slr * lamb_u(m[k], v[k], wk, rbc1, rbc2, hp.eps, wd);
+    w[k] = wk;
+    if (model) st1(model + k, wk);
+  }
+}
+
 // Adasum merge: a <- ca*a + cb*b with ca = 1 - a.b/(2|a|^2), cb = 1 - a.b/(2|b|^2)
 template <typename T>
 __global__ __launch_bounds__(kBlock) void adasum_combine_kernel(T* __restrict__ a,
@@ -684,6 +818,39 @@ void mv_launch_lars(const void* g, int gd, float* w, float* mom, void* model, in
   DISPATCH_GP(gd, md, hipLaunchKernelGGL((lars_flat_kernel<TG, TP>), dim3(ct.nchunks), dim3(kBlock),
                                          0, st, (const TG*)g, w, mom, (TP*)model, ct.begin, ct.len,
                                          ct.seg, sflag, norms, hp, dyn, skip));
+}
+
+void mv_launch_lamb(const void* g, int gd, float* w, float* m, float* v, void* model, int md,
+                    const ChunkTable& ct, const int32_t* sflag, float* partial, float* norms,
+                    float lr, double b1, double b2, float eps, float wd, float gscale, float bc1,
+                    float bc2, const float* dyn, const int* skip, hipStream_t st) {
+  if (ct.nchunks <= 0) return;
+  LambHp hp{lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), eps, wd, gscale,
+            bc1, bc2};
+  // stage 1: m, v and per-chunk (|w|^2, |u|^2)
+#define MV_LAMB1(TG)                                                                            \
+  hipLaunchKernelGGL((lamb_moments_kernel<TG>), dim3(ct.nchunks), dim3(kBlock), 0, st,           \
+                     (const TG*)g, (const float*)w, m, v, ct.begin, ct.len, ct.seg, sflag,       \
+                     partial, hp, dyn, skip)
+  switch (gd) {
+    case F32: MV_LAMB1(float); break;
+    case BF16: MV_LAMB1(__bf16); break;
+    case F16: MV_LAMB1(_Float16); break;
+  }
+#undef MV_LAMB1
+  hipLaunchKernelGGL((seg_reduce_kernel<2>), dim3(ct.nseg), dim3(kWave), 0, st, partial, ct.seg_c0,
+                     ct.seg_nc, norms, 0);
+  // stage 2: the update, from the stored m and v (the gradient is not read again)
+#define MV_LAMB2(TP)                                                                            \
+  hipLaunchKernelGGL((lamb_apply_kernel<TP>), dim3(ct.nchunks), dim3(kBlock), 0, st, w,          \
+                     (const float*)m, (const float*)v, (TP*)model, ct.begin, ct.len, ct.seg,     \
+                     sflag, (const float*)norms, hp, dyn, skip)
+  switch (md) {
+    case F32: MV_LAMB2(float); break;
+    case BF16: MV_LAMB2(__bf16); break;
+    case F16: MV_LAMB2(_Float16); break;
+  }
+#undef MV_LAMB2
 }
 
 void mv_launch_seg_dot3(const void* a, const void* b, int dt, const ChunkTable& ct, float* partial,

@@ -305,6 +305,51 @@ def lars_step(g, w, mom, model, table: ChunkTable, seg_flags: torch.Tensor, *, l
             model[sl].copy_(wi)
 
 
+def lamb_step(g, w, m, v, model, table: ChunkTable, seg_flags: torch.Tensor, *, lr, beta1=0.9,
+              beta2=0.999, eps=1e-6, weight_decay=0.0, gscale=1.0, step=1,
+              workspace: Optional[dict] = None, dyn=None, skip=None):
+    """Segmented LAMB (You et al. 2019).  Per segment, with gr = g * gscale:
+    m = b1 m + (1-b1) gr, v = b2 v + (1-b2) gr^2, u = (m/bc1) / (sqrt(v/bc2) + eps) + wd w,
+    trust = |w| / |u| when both norms are positive (else 1), w -= lr trust u.  Flagged
+    segments (bit0) get trust 1 and no weight decay.  ``dyn`` overrides lr, bc1 and bc2;
+    ``skip`` leaves w, m, v and the model copy untouched.  On the GPU the workspace keeps
+    ``norms`` = (|w|^2, |u|^2) per segment of the last call."""
+    _check_table(table, g.numel())
+    if _on_gpu(g):
+        ws = workspace if workspace is not None else {}
+        partial = ws.get("partial")
+        if partial is None or partial.numel() < 2 * table.nchunks:
+            partial = ws["partial"] = torch.empty(2 * table.nchunks, dtype=torch.float32,
+                                                  device=g.device)
+        norms = ws.get("norms")
+        if norms is None or norms.numel() < 2 * table.nseg:
+            norms = ws["norms"] = torch.empty(2 * table.nseg, dtype=torch.float32, device=g.device)
+        native()._lamb.lamb_step(g, w, m, v, model, table.begin, table.len, table.seg,
+                                 table.seg_c0, table.seg_nc, seg_flags, partial, norms, float(lr),
+                                 float(beta1), float(beta2), float(eps), float(weight_decay),
+                                 float(gscale), int(step), dyn, skip)
+        return
+    if _skipped(skip):
+        return
+    bc1 = 1 - beta1 ** step
+    bc2 = 1 - beta2 ** step
+    flags = seg_flags.tolist()
+    for i, (off, n) in enumerate(zip(table.seg_offsets, table.seg_sizes)):
+        sl = slice(off, off + n)
+        wi, mi, vi = w[sl], m[sl], v[sl]
+        gr = g[sl].float() * gscale
+        plain = flags[i] & 1
+        wd = 0.0 if plain else weight_decay
+        mi.mul_(beta1).add_(gr, alpha=1 - beta1)
+        vi.mul_(beta2).addcmul_(gr, gr, value=1 - beta2)
+        u = (mi / bc1) / (vi.sqrt() / math.sqrt(bc2) + eps) + wd * wi
+        wn, un = math.sqrt(float((wi * wi).sum())), math.sqrt(float((u * u).sum()))
+        trust = wn / un if (not plain and wn > 0 and un > 0) else 1.0
+        wi.sub_(u, alpha=lr * trust)
+        if model is not None:
+            model[sl].copy_(wi)
+
+
 def seg_dot3(a: torch.Tensor, b: torch.Tensor, table: ChunkTable,
              workspace: Optional[dict] = None) -> torch.Tensor:
     """Per segment (a.b, |a|^2, |b|^2) as a [nseg, 3] fp32 tensor (deterministic).

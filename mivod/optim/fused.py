@@ -343,3 +343,37 @@ class FusedLARS(FusedOptimizer):
                     momentum=hp["momentum"], weight_decay=hp["weight_decay"], eta=hp["eta"],
                     gscale=gscale, eps=hp["eps"], first=(a.step == 1), workspace=a.workspace,
                     dyn=self._mv_dyn(a), skip=self._mv_skip)
+
+
+class FusedLAMB(FusedOptimizer):
+    """LAMB (You et al. 2019, arXiv 1904.00962): Adam moments with bias correction and
+    decoupled weight decay inside the update direction, scaled per parameter tensor by the
+    trust ratio |w| / |u|.  Parameters with ``dim() <= 1`` (biases, LayerNorm) take no
+    weight decay and trust 1 when ``exclude_1d=True``; with ``exclude_1d=False`` every
+    tensor is adapted and decayed.
+
+    Not provided: global gradient-norm clipping (``max_grad_norm``: it needs every bucket
+    reduced before the first update, which the overlapped per-bucket step does not wait
+    for), trust-ratio clamping, ``grad_averaging=False`` and an ``always_adapt`` switch."""
+
+    _state_names = ["exp_avg", "exp_avg_sq"]
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01,
+                 exclude_1d=True, grad_dtype=None):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      exclude_1d=exclude_1d), grad_dtype)
+        self._mv_flags: Dict[tuple, torch.Tensor] = {}
+
+    def _mv_apply(self, a, i0, i1, gscale=1.0):
+        g, w, st, model = self._mv_slices(a, i0, i1)
+        hp = a.group
+        key = (id(a), i0, i1)
+        flags = self._mv_flags.get(key)
+        if flags is None:
+            fl = [1 if (hp["exclude_1d"] and a.params[i].dim() <= 1) else 0 for i in range(i0, i1)]
+            flags = self._mv_flags[key] = torch.tensor(fl, dtype=torch.int32, device=a.device)
+        b1, b2 = hp["betas"]
+        K.lamb_step(g, w, st["exp_avg"], st["exp_avg_sq"], model, a.table(i0, i1), flags,
+                    lr=hp["lr"], beta1=b1, beta2=b2, eps=hp["eps"],
+                    weight_decay=hp["weight_decay"], gscale=gscale, step=a.step,
+                    workspace=a.workspace, dyn=self._mv_dyn(a), skip=self._mv_skip)
