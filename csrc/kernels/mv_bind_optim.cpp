@@ -1,4 +1,6 @@
-// mivod._mvk bindings: multi-tensor pack / cast, fused optimizer steps, Adasum (mv_kernels.h)
+// mivod._mvk bindings: multi-tensor pack / cast, fused optimizer steps, Adasum (mv_kernels.h,
+// mv_adaptive.h)
+#include "mv_adaptive.h"
 #include "mv_checks.h"
 #include "mv_kernels.h"
 
@@ -76,7 +78,8 @@ void nonfinite_scan(at::Tensor x, at::Tensor flag) {
 
 // The flat SGD / Adam / Adadelta kernels move 8 elements per lane with 16-byte accesses and
 // have no scalar fallback (the arenas hand them 64-element-aligned slices), so an offset
-// view is an error here; LARS and LAMB guard their vector bodies themselves and take any offset.
+// view is an error here; LARS, LAMB, RMSprop and Adagrad guard their vector bodies themselves
+// and take any offset.
 void check_aligned16(const char* fn, const char* what, const void* p) {
   TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 15u) == 0, fn, ": ", what,
               " must be 16-byte aligned");
@@ -211,6 +214,33 @@ void lamb_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
                  s.dyn, s.skip, cur_stream());
 }
 
+// RMSprop / Adagrad (mv_adaptive.hip).  grad_avg given: centered; momentum_buffer given: momentum.
+void rmsprop_step(at::Tensor g, at::Tensor w, at::Tensor sq, c10::optional<at::Tensor> ga,
+                  c10::optional<at::Tensor> buf, c10::optional<at::Tensor> model, double lr,
+                  double alpha, double eps, double wd, double momentum, double gscale,
+                  c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
+  const StepArgs s = step_args("rmsprop_step", g, w, model, dyn, skip, false);
+  float* sp = vec_ptr("rmsprop_step", "square_avg", sq, g, g.numel());
+  float* gp = vec_ptr_opt("rmsprop_step", "grad_avg", ga, g, g.numel());
+  float* bp = vec_ptr_opt("rmsprop_step", "momentum_buffer", buf, g, g.numel());
+  TORCH_CHECK(bp != nullptr || momentum == 0.0,
+              "rmsprop_step: momentum_buffer must be given when momentum != 0");
+  c10::DeviceGuard guard(g.device());
+  mv_launch_rmsprop(g.data_ptr(), dtype_code(g), s.w, sp, gp, bp, s.model, s.model_dt, g.numel(),
+                    (float)lr, alpha, (float)eps, (float)wd, (float)momentum, (float)gscale, s.dyn,
+                    s.skip, cur_stream());
+}
+
+void adagrad_step(at::Tensor g, at::Tensor w, at::Tensor sum, c10::optional<at::Tensor> model,
+                  double lr, double eps, double wd, double gscale, c10::optional<at::Tensor> dyn,
+                  c10::optional<at::Tensor> skip) {
+  const StepArgs s = step_args("adagrad_step", g, w, model, dyn, skip, false);
+  float* sp = vec_ptr("adagrad_step", "sum", sum, g, g.numel());
+  c10::DeviceGuard guard(g.device());
+  mv_launch_adagrad(g.data_ptr(), dtype_code(g), s.w, sp, s.model, s.model_dt, g.numel(),
+                    (float)lr, (float)eps, (float)wd, (float)gscale, s.dyn, s.skip, cur_stream());
+}
+
 void seg_dot3(at::Tensor a, at::Tensor b, at::Tensor cbeg, at::Tensor clen, at::Tensor cseg,
               at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor partial, at::Tensor out,
               bool swap) {
@@ -297,6 +327,11 @@ void bind_optim(pybind11::module_& m) {
   pybind11::module_ lb = m.def_submodule(
       "_lamb", "LAMB: Adam moments with a per-segment trust ratio on the flat-arena path");
   lb.def("lamb_step", &lamb_step, "fused segmented LAMB step");
+  // so have RMSprop and Adagrad: mivod._mvk._adaptive
+  pybind11::module_ ad = m.def_submodule(
+      "_adaptive", "RMSprop and Adagrad steps on the flat-arena path");
+  ad.def("rmsprop_step", &rmsprop_step, "fused flat RMSprop step (centered / momentum optional)");
+  ad.def("adagrad_step", &adagrad_step, "fused flat Adagrad step");
   m.def("seg_dot3", &seg_dot3, "per-segment (a.b, |a|^2, |b|^2) (swap: (a.b, |b|^2, |a|^2))");
   m.def("adasum_merge", &adasum_merge,
         "one vector-halving Adasum level: merge with fixed-order group Gram sums + fused wire cast");

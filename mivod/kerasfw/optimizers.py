@@ -8,8 +8,10 @@ explains why the reference must keep Keras on that path); ``get_config`` /
 ``from_config`` drive re-instantiation and ``load_model``.
 
 The update itself is a mivod fused kernel (FusedAdadelta / FusedAdam with
-Keras epsilon placement / FusedSGD): one launch per arena on the GPU, the
-plain-PyTorch reference math on the CPU.
+Keras epsilon placement / FusedSGD / FusedRMSprop / FusedAdagrad): one launch
+per arena on the GPU, the plain-PyTorch reference math on the CPU.  RMSprop and
+Adagrad keep torch's form (epsilon outside the root; RMSprop's rate outside its
+momentum buffer): see their docstrings for what that changes against tf.keras.
 """
 from __future__ import annotations
 
@@ -192,20 +194,53 @@ def epsilon_default():
 
 
 class RMSprop(Optimizer):
+    """RMSprop on ``FusedRMSprop`` (torch.optim.RMSprop semantics): ``rho`` is the decay of the
+    squared-gradient average and ``epsilon`` is added outside the root, which with the defaults
+    is what tf.keras computes up to the placement of epsilon.  With ``momentum > 0`` the form
+    differs from tf.keras: there the buffer accumulates ``lr * g / sqrt(avg + epsilon)`` (the
+    rate inside the buffer, epsilon inside the root); here it accumulates
+    ``g / (sqrt(avg) + epsilon)`` and the rate multiplies the buffer, so a rate changed during
+    training rescales the steps already accumulated.  ``momentum`` and ``centered`` are fixed
+    once the first step has built the optimizer state."""
     _default_lr = 0.001
-    _hyper = ("rho", "epsilon")
+    _hyper = ("rho", "epsilon", "momentum", "centered")
 
-    def __init__(self, lr=None, rho=0.9, epsilon=None, decay=0.0, name=None, **kw):
+    def __init__(self, lr=None, rho=0.9, epsilon=None, decay=0.0, momentum=0.0, centered=False,
+                 name=None, **kw):
         kw.setdefault("lr", lr if lr is not None else self._default_lr)
         super().__init__(name=name, decay=decay, **kw)
         self.rho = float(rho)
         self.epsilon = float(epsilon if epsilon is not None else 1e-7)
+        self.momentum = Variable(momentum, "momentum")
+        self.centered = bool(centered)
 
     def _make_impl(self, params):
-        return torch.optim.RMSprop(params, lr=float(self.lr), alpha=self.rho, eps=self.epsilon)
+        from ..optim import FusedRMSprop
+        return FusedRMSprop(params, lr=float(self.lr), alpha=self.rho, eps=self.epsilon,
+                            momentum=float(self.momentum) or 0.0, centered=self.centered)
 
 
-OPTIMIZERS = {"SGD": SGD, "Adam": Adam, "Adadelta": Adadelta, "RMSprop": RMSprop}
+class Adagrad(Optimizer):
+    """Adagrad on ``FusedAdagrad``; ``decay`` is the base class's rate decay
+    lr / (1 + decay * iterations), the same schedule as torch's ``lr_decay``."""
+    _default_lr = 0.001
+    _hyper = ("initial_accumulator_value", "epsilon")
+
+    def __init__(self, lr=None, initial_accumulator_value=0.1, epsilon=None, decay=0.0, name=None,
+                 **kw):
+        kw.setdefault("lr", lr if lr is not None else self._default_lr)
+        super().__init__(name=name, decay=decay, **kw)
+        self.initial_accumulator_value = float(initial_accumulator_value)
+        self.epsilon = float(epsilon if epsilon is not None else 1e-7)
+
+    def _make_impl(self, params):
+        from ..optim import FusedAdagrad
+        return FusedAdagrad(params, lr=float(self.lr), eps=self.epsilon,
+                            initial_accumulator_value=self.initial_accumulator_value)
+
+
+OPTIMIZERS = {"SGD": SGD, "Adam": Adam, "Adadelta": Adadelta, "RMSprop": RMSprop,
+              "Adagrad": Adagrad}
 
 
 def get(opt):

@@ -199,6 +199,62 @@ def adadelta_step(g, w, sq, acc, model, *, lr=1.0, rho=0.9, eps=1e-6, weight_dec
         model.copy_(w)
 
 
+def rmsprop_step(g, w, sq, ga, buf, model, *, lr, alpha=0.99, eps=1e-8, weight_decay=0.0,
+                 momentum=0.0, centered=False, gscale=1.0, dyn=None, skip=None):
+    """RMSprop with torch.optim.RMSprop's semantics (eps outside the root, lr outside the
+    momentum buffer).  With gr = g * gscale + wd * w: sq = alpha sq + (1-alpha) gr^2;
+    centered: ga = alpha ga + (1-alpha) gr and avg = sqrt(max(sq - ga^2, 0)) + eps, else
+    avg = sqrt(sq) + eps; with a momentum buffer buf = momentum buf + gr / avg and
+    w -= lr buf, else w -= lr gr / avg.  The clamp at zero is the one deviation from torch,
+    whose root of a difference that rounded below zero is NaN.  ``ga`` (``buf``) is the state
+    of ``centered`` (``momentum``) and may be None without it; ``dyn[0]`` replaces ``lr``."""
+    if centered and ga is None:
+        raise ValueError("rmsprop_step: centered needs the grad_avg buffer")
+    if momentum != 0 and buf is None:
+        raise ValueError("rmsprop_step: momentum needs the momentum buffer")
+    if not centered:
+        ga = None
+    if _on_gpu(g):
+        native()._adaptive.rmsprop_step(g, w, sq, ga, buf, model, float(lr), float(alpha),
+                                        float(eps), float(weight_decay), float(momentum),
+                                        float(gscale), dyn, skip)
+        return
+    if _skipped(skip):
+        return
+    gr = g.float() * gscale + weight_decay * w
+    sq.mul_(alpha).addcmul_(gr, gr, value=1 - alpha)
+    if ga is not None:
+        ga.mul_(alpha).add_(gr, alpha=1 - alpha)
+        avg = (sq - ga * ga).clamp_(min=0).sqrt_().add_(eps)
+    else:
+        avg = sq.sqrt().add_(eps)
+    q = gr / avg
+    if buf is not None:
+        buf.mul_(momentum).add_(q)
+        q = buf
+    w.sub_(lr * q)
+    if model is not None:
+        model.copy_(w)
+
+
+def adagrad_step(g, w, sum, model, *, lr, eps=1e-10, weight_decay=0.0, gscale=1.0, dyn=None,
+                 skip=None):
+    """Adagrad with torch.optim.Adagrad's semantics: gr = g * gscale + wd * w, sum += gr^2,
+    w -= lr gr / (sqrt(sum) + eps).  ``lr`` is the decayed rate lr0 / (1 + (step-1) lr_decay)
+    of this step, taken by the caller; ``dyn[0]`` replaces it."""
+    if _on_gpu(g):
+        native()._adaptive.adagrad_step(g, w, sum, model, float(lr), float(eps),
+                                        float(weight_decay), float(gscale), dyn, skip)
+        return
+    if _skipped(skip):
+        return
+    gr = g.float() * gscale + weight_decay * w
+    sum.addcmul_(gr, gr)
+    w.sub_(lr * (gr / sum.sqrt().add_(eps)))
+    if model is not None:
+        model.copy_(w)
+
+
 # ---------------------------------------------------------------------------
 # Segment / chunk tables (LARS, Adasum)
 # ---------------------------------------------------------------------------

@@ -377,3 +377,68 @@ class FusedLAMB(FusedOptimizer):
                     lr=hp["lr"], beta1=b1, beta2=b2, eps=hp["eps"],
                     weight_decay=hp["weight_decay"], gscale=gscale, step=a.step,
                     workspace=a.workspace, dyn=self._mv_dyn(a), skip=self._mv_skip)
+
+
+class FusedRMSprop(FusedOptimizer):
+    """RMSprop with torch.optim.RMSprop's semantics and state names (``square_avg``,
+    ``momentum_buffer`` when ``momentum != 0``, ``grad_avg`` when ``centered``), so a
+    torch.optim.RMSprop state dict loads.  One deviation: the centered variance
+    ``square_avg - grad_avg^2`` is clamped at zero before the root (rounded, it can fall
+    below zero, where torch produces NaN).  ``momentum`` and ``centered`` decide which state
+    arenas exist, so they are fixed at construction; a group's momentum may change between
+    non-zero values."""
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0,
+                 centered=False, grad_dtype=None):
+        if lr < 0 or eps < 0 or alpha < 0 or momentum < 0 or weight_decay < 0:
+            raise ValueError("FusedRMSprop: lr, alpha, eps, momentum and weight_decay must be >= 0")
+        self._state_names = (["square_avg"] + (["momentum_buffer"] if momentum != 0 else [])
+                             + (["grad_avg"] if centered else []))
+        super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay,
+                                      momentum=momentum, centered=bool(centered)), grad_dtype)
+
+    def _mv_apply(self, a, i0, i1, gscale=1.0):
+        g, w, st, model = self._mv_slices(a, i0, i1)
+        hp = a.group
+        K.rmsprop_step(g, w, st["square_avg"], st.get("grad_avg"), st.get("momentum_buffer"), model,
+                       lr=hp["lr"], alpha=hp["alpha"], eps=hp["eps"],
+                       weight_decay=hp["weight_decay"], momentum=hp["momentum"],
+                       centered=hp["centered"], gscale=gscale, dyn=self._mv_dyn(a),
+                       skip=self._mv_skip)
+
+
+class FusedAdagrad(FusedOptimizer):
+    """Adagrad with torch.optim.Adagrad's semantics and state name (``sum``, filled with
+    ``initial_accumulator_value`` when the arenas are built).  The decayed rate
+    lr / (1 + (step-1) lr_decay) is taken on the host, so a captured HIP graph, whose device
+    hyperparameter block carries the rate but no step count, refuses ``lr_decay != 0``."""
+
+    _state_names = ["sum"]
+
+    def __init__(self, params, lr=1e-2, lr_decay=0, weight_decay=0, initial_accumulator_value=0,
+                 eps=1e-10, grad_dtype=None):
+        if lr < 0 or lr_decay < 0 or weight_decay < 0 or initial_accumulator_value < 0 or eps < 0:
+            raise ValueError("FusedAdagrad: lr, lr_decay, weight_decay, "
+                             "initial_accumulator_value and eps must be >= 0")
+        super().__init__(params, dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay,
+                                      initial_accumulator_value=initial_accumulator_value),
+                         grad_dtype)
+
+    def _mv_build(self, grad_dtype_for=None):
+        if self._mv_arenas is None:
+            # the alignment gaps hold the value too: their gradients are zero, so they stay put
+            for a in super()._mv_build(grad_dtype_for):
+                a.state["sum"].fill_(float(a.group["initial_accumulator_value"]))
+        return self._mv_arenas
+
+    def _mv_apply(self, a, i0, i1, gscale=1.0):
+        g, w, st, model = self._mv_slices(a, i0, i1)
+        hp = a.group
+        if hp["lr_decay"] != 0 and self._mv_graph:
+            raise NotImplementedError(
+                "FusedAdagrad: lr_decay != 0 under HIP-graph capture (the replayed "
+                "hyperparameter block carries lr but no step count)")
+        clr = hp["lr"] / (1.0 + (a.step - 1) * hp["lr_decay"])
+        K.adagrad_step(g, w, st["sum"], model, lr=clr, eps=hp["eps"],
+                       weight_decay=hp["weight_decay"], gscale=gscale, dyn=self._mv_dyn(a),
+                       skip=self._mv_skip)
