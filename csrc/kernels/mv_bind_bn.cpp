@@ -86,6 +86,7 @@ at::Tensor bn_apply(at::Tensor x, at::Tensor scale, at::Tensor bias, bool relu,
   const void* rp = opt_same("bn_apply", "residual", residual, x);
   c10::DeviceGuard guard(x.device());
   at::Tensor y = at::empty_like(x);
+  if (M == 0) return y;   // an empty batch (eval): nothing to launch
   mv_bn_apply(x.data_ptr(), rp, y.data_ptr(), M, (int)C, sp, bp, relu, cur_stream());
   return y;
 }
@@ -159,6 +160,7 @@ std::vector<at::Tensor> bn_bwd(int64_t mode, at::Tensor dy, at::Tensor x,
   const int64_t M = check_act("bn_bwd", "x", x, dy, &C);
   TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(),
               "bn_bwd: dy must match x in shape and layout");
+  TORCH_CHECK(M > 0, "bn_bwd: empty input");
   TORCH_CHECK(mode >= 0 && mode <= 3, "bn_bwd: bad mode");
   const float* vp = vec_ptr("bn_bwd", "vec", vec, x, 4 * C);
   const float* gp = vec_ptr_opt("bn_bwd", "weight", gamma, x, C);

@@ -72,7 +72,8 @@ inline int64_t check_act(const char* fn, const char* what, const at::Tensor& t,
                   (t.dim() == 2 && t.is_contiguous()),
               fn, ": ", what, " must be channels_last 4-D or contiguous 2-D");
   *C = t.size(1);
-  TORCH_CHECK(*C % 8 == 0, fn, ": ", what, " must have a channel count that is a multiple of 8");
+  TORCH_CHECK(*C > 0 && *C % 8 == 0, fn, ": ", what,
+              " must have a channel count that is a multiple of 8");
   return t.numel() / *C;
 }
 

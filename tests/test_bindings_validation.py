@@ -232,6 +232,38 @@ def test_bn_apply_rejects_strided_scale(cuda):
 
 
 @pytest.mark.gpu
+def test_bn_activation_without_channels_is_rejected(cuda):
+    """[M, 0] passes C % 8 == 0; the row count M = numel / C must not be computed from it."""
+    with pytest.raises(RuntimeError, match="bn_stats: x must have a channel count"):
+        mvk.bn_stats(t(4, 0, device=cuda), None, None, None, None, 0.1, 1e-5)
+    with pytest.raises(RuntimeError, match="bn_apply: x must have a channel count"):
+        mvk.bn_apply(t(4, 0, device=cuda), t(0, dtype=f32, device=cuda),
+                     t(0, dtype=f32, device=cuda), True, None)
+
+
+@pytest.mark.gpu
+def test_bn_apply_returns_an_empty_batch(cuda):
+    """No launch for zero rows: the empty y, as stock PyTorch's eval BatchNorm returns."""
+    from mivod.ops.bn import batch_norm_act
+    sc, bi = t(64, dtype=f32, device=cuda), t(64, dtype=f32, device=cuda)
+    for x in (t(0, 64, device=cuda), cl(0, 64, 8, 8, device=cuda)):
+        y = mvk.bn_apply(x, sc, bi, True, None)
+        assert y.shape == x.shape and y.dtype == bf16 and y.numel() == 0
+    x = cl(0, 64, 8, 8, device=cuda)
+    with torch.no_grad():
+        y = batch_norm_act(x, sc + 1, bi, bi.clone(), sc + 1, False, 0.1, 1e-5, True, None)
+    assert y.shape == x.shape and y.numel() == 0
+    torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+def test_bn_bwd_rejects_an_empty_batch(cuda):
+    x = t(0, 64, device=cuda)
+    with pytest.raises(RuntimeError, match="bn_bwd: empty input"):
+        mvk.bn_bwd(0, x, x.clone(), None, t(4, 64, dtype=f32, device=cuda), None, True, None, 1)
+
+
+@pytest.mark.gpu
 def test_secondary_operand_on_another_gpu_is_rejected(cuda):
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs")
