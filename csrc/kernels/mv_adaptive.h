@@ -18,7 +18,8 @@ void mv_launch_rmsprop(const void* g, int gd, float* w, float* sq, float* ga, fl
                        float momentum, float gscale, const float* dyn, const int* skip,
                        hipStream_t st);
 // torch.optim.Adagrad: sum += gr^2, w -= lr * gr / (sqrt(sum) + eps); lr is the decayed rate
-// lr0 / (1 + (step-1)*lr_decay), taken by the caller in double.
+// lr0 / (1 + (step-1)*lr_decay), taken by the caller in double.  sum must not be null: the
+// kernel tells the compiler so (__builtin_assume).
 void mv_launch_adagrad(const void* g, int gd, float* w, float* sum, void* model, int md, int64_t n,
                        float lr, float eps, float wd, float gscale, const float* dyn,
                        const int* skip, hipStream_t st);

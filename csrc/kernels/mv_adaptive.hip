@@ -1,19 +1,17 @@
 // mivod gfx950 kernels: RMSprop and Adagrad on flat buckets (K6, next to mv_kernels.hip's
-// SGD / Adam / Adadelta).  Pure streaming updates in the shape of adadelta_flat_kernel: one
-// workgroup of 256 lanes per 4096-element chunk, 8 elements per lane per step through
-// load8 / store8 (16-byte accesses), a scalar tail for the last n % 8 elements, the gradient
-// read once in the wire dtype (TG), fp32 master and state read and written once, the optional
-// low-precision model copy (TP) written in the same pass.
+// SGD / Adam / Adadelta).  Pure streaming updates: one workgroup of 256 lanes per 4096-element
+// chunk, 8 elements per lane per step through load8 / store8 (16-byte accesses), a scalar tail
+// for the last n % 8 elements, the gradient read once in the wire dtype (TG), fp32 master and
+// state read and written once, the optional low-precision model copy (TP) written in the same
+// pass.  Adagrad is its arithmetic on mv_flat_step.h's skeleton; RMSprop is the same loop
+// written out (that header says why).  Both guard their vector body: when any base pointer
+// is not 16-byte aligned (an offset view; the arenas never produce one) every element goes
+// through the scalar path, uniformly over the launch.
 //
 // Bytes per element with an fp16 wire and a bf16 model: g 2 + w 4+4 + model 2 = 12, plus 8 per
 // state buffer: 20 (plain RMSprop, Adagrad), 28 (momentum or centered), 36 (both).
-//
-// Unlike the SGD / Adam / Adadelta kernels these guard their vector body themselves: when any
-// base pointer is not 16-byte aligned (an offset view; the arenas never produce one) every
-// element goes through the scalar path.  Chunks start at multiples of 4096 elements, so the
-// alignment of the bases decides it for the whole launch and the branch is uniform.
 #include "mv_adaptive.h"
-#include "mv_common.h"
+#include "mv_flat_step.h"
 
 using namespace mv;
 
@@ -101,65 +99,18 @@ __global__ __launch_bounds__(kBlock) void adagrad_flat_kernel(const TG* __restri
                                                                const int* __restrict__ skip) {
   if (skip && *skip) return;
   if (dyn) hp.lr = dyn[0];
-  const bool vec = aligned16(g) && aligned16(w) && aligned16(sum) && aligned16_or_null(model);
-  const int64_t base = (int64_t)blockIdx.x * kChunk;
-  for (int64_t i = base + threadIdx.x * kVec; i < base + kChunk; i += kBlock * kVec) {
-    const int cnt = (i + kVec <= n) ? kVec : (i < n ? (int)(n - i) : 0);
-    if (cnt == 0) break;
-    const bool full = vec && cnt == kVec;
-    float gv[8], wv[8], sv[8];
-    if (full) {
-      load8(g + i, gv); load8(w + i, wv); load8(sum + i, sv);
-    } else {
-      for (int j = 0; j < kVec; ++j) {
-        gv[j] = j < cnt ? ld1(g + i + j) : 0.f; wv[j] = j < cnt ? w[i + j] : 0.f;
-        sv[j] = j < cnt ? sum[i + j] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gr = gv[j] * hp.gscale + hp.wd * wv[j];
-      sv[j] += gr * gr;
-      wv[j] -= hp.lr * (gr / (sqrtf(sv[j]) + hp.eps));
-    }
-    if (full) {
-      store8(w + i, wv); store8(sum + i, sv);
-      if (model) store8(model + i, wv);
-    } else {
-      for (int j = 0; j < cnt; ++j) {
-        w[i + j] = wv[j]; sum[i + j] = sv[j];
-        if (model) st1(model + i + j, wv[j]);
-      }
-    }
-  }
+  __builtin_assume(sum != nullptr);   // always given: drops flat_step's null tests, as in Adam
+  float* const st[1] = {sum};
+  flat_step<1>(g, w, st, model, n, [&](float gj, float& wj, float& sj) {
+    const float gr = gj * hp.gscale + hp.wd * wj;
+    sj += gr * gr;
+    wj -= hp.lr * (gr / (sqrtf(sj) + hp.eps));
+  });
 }
 
 }  // namespace mv
 
-// ---------------- host launchers ----------------
-// MV_GRID and DISPATCH_GP are mv_kernels.hip's, which defines them for itself in its .hip file
-#define MV_GRID(n) dim3((unsigned)(((n) + kChunk - 1) / kChunk))
-
-#define DISPATCH_GP(gd, md, MACRO)                                  \
-  do {                                                              \
-    if (md == F32) {                                                \
-      using TP = float;                                             \
-      if (gd == F32) { using TG = float; MACRO; }                   \
-      else if (gd == BF16) { using TG = __bf16; MACRO; }            \
-      else { using TG = _Float16; MACRO; }                          \
-    } else if (md == BF16) {                                        \
-      using TP = __bf16;                                            \
-      if (gd == F32) { using TG = float; MACRO; }                   \
-      else if (gd == BF16) { using TG = __bf16; MACRO; }            \
-      else { using TG = _Float16; MACRO; }                          \
-    } else {                                                        \
-      using TP = _Float16;                                          \
-      if (gd == F32) { using TG = float; MACRO; }                   \
-      else if (gd == BF16) { using TG = __bf16; MACRO; }            \
-      else { using TG = _Float16; MACRO; }                          \
-    }                                                               \
-  } while (0)
-
+// ---------------- host launchers (MV_GRID, DISPATCH_GP: mv_flat_step.h) ----------------
 void mv_launch_rmsprop(const void* g, int gd, float* w, float* sq, float* ga, float* buf,
                        void* model, int md, int64_t n, float lr, double alpha, float eps, float wd,
                        float momentum, float gscale, const float* dyn, const int* skip,

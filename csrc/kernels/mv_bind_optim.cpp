@@ -76,10 +76,11 @@ void nonfinite_scan(at::Tensor x, at::Tensor flag) {
   mv_launch_nonfinite_scan(x.data_ptr(), dtype_code(x), x.numel(), fp, cur_stream());
 }
 
-// The flat SGD / Adam / Adadelta kernels move 8 elements per lane with 16-byte accesses and
-// have no scalar fallback (the arenas hand them 64-element-aligned slices), so an offset
-// view is an error here; LARS, LAMB, RMSprop and Adagrad guard their vector bodies themselves
-// and take any offset.
+// sgd_step / adam_step / adadelta_step refuse an operand that is not 16-byte aligned.  Their
+// kernels (on mv_flat_step.h's skeleton, which guards its vector body) would take an offset
+// view, but the binding keeps refusing one: the arenas hand all three 64-element-aligned
+// slices, that is their contract and the existing behaviour.  LARS, LAMB, RMSprop and Adagrad
+// take any offset.
 void check_aligned16(const char* fn, const char* what, const void* p) {
   TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 15u) == 0, fn, ": ", what,
               " must be 16-byte aligned");

@@ -38,6 +38,8 @@ void mv_launch_sgd(const void* g, int gd, float* w, float* mom, void* model, int
 // (fp16-wire overflow guard, identical on every rank after the flag allreduce)
 // dyn (nullable): device [lr, first, bc1, bc2] read by the kernel instead of the
 // scalar arguments — HIP-graph replayable hyperparameters (mivod/torch/graphs.py)
+// m, v (Adam) and sq, acc (Adadelta) must not be null: the kernels tell the compiler so
+// (__builtin_assume), and a null one is undefined behaviour, not a skipped stream
 void mv_launch_adam(const void* g, int gd, float* w, float* m, float* v, void* model, int md,
                     int64_t n, float lr, double b1, double b2, float eps, float wd, float gscale,
                     float bc1, float bc2, int adamw, int keras_eps, const float* dyn,

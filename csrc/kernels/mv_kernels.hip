@@ -9,13 +9,15 @@
 //   K6     mv_{sgd,adam,adadelta}_flat, mv_lars_*, mv_lamb_*  fused optimizer steps that
 //                            run directly on a reduced flat gradient bucket,
 //                            fp32 master weights + bf16 model copy written in
-//                            the same pass (grad read once)
+//                            the same pass (grad read once); SGD, Adam and Adadelta
+//                            on the streaming skeleton of mv_flat_step.h
 //   K8     mv_seg_dot3 / mv_adasum_combine  Adasum per-tensor Gram terms and
 //                            the (1-d/2|a|^2)a + (1-d/2|b|^2)b merge
 // See SURVEY.md §2.5.b for the inventory.  All kernels are HBM-bound: the design
 // goal is 16-byte lanes, >=1k workgroups per launch and a single pass over
 // every byte (no separate scale / cast / unscale passes).
 #include "mv_common.h"
+#include "mv_flat_step.h"
 #include "mv_kernels.h"
 
 #include <type_traits>
@@ -217,6 +219,9 @@ void mv_launch_nonfinite_scan(const void* x, int dt, int64_t n, int* flag, hipSt
 // grad (TG: the wire / bucket dtype), fp32 master + fp32 state, and an optional
 // low-precision model copy (TP) written in the same pass.  Arena segments are
 // 64-element aligned, so the vector path covers everything but a final tail.
+// SGD, Adam and Adadelta are a prologue and the arithmetic on one element, handed
+// to flat_step (mv_flat_step.h: the loads, the stores, the alignment guard, the
+// tail, and why LARS is not on it).
 // -------------------------------------------------------------------------
 namespace mv {
 
@@ -246,41 +251,16 @@ __global__ __launch_bounds__(kBlock) void sgd_flat_kernel(const TG* __restrict__
                                                            const int* __restrict__ skip) {
   if (skip && *skip) return;   // overflow guard: every rank skips this step identically
   if (dyn) { hp.lr = dyn[0]; hp.first = dyn[1] != 0.f; }
-  const int64_t base = (int64_t)blockIdx.x * kChunk;
-  for (int64_t i = base + threadIdx.x * kVec; i < base + kChunk; i += kBlock * kVec) {
-    if (i + kVec <= n) {
-      float gv[8], wv[8], mv_[8];
-      load8(g + i, gv);
-      load8(w + i, wv);
-      if (mom) load8(mom + i, mv_);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float d = gv[j] * hp.gscale + hp.wd * wv[j];
-        if (mom) {
-          float b = hp.first ? d : hp.momentum * mv_[j] + hp.omd * d;
-          mv_[j] = b;
-          d = hp.nesterov ? d + hp.momentum * b : b;
-        }
-        wv[j] -= hp.lr * d;
-      }
-      store8(w + i, wv);
-      if (mom) store8(mom + i, mv_);
-      if (model) store_model(model + i, wv);
-    } else {
-      for (int64_t k = i; k < n && k < i + kVec; ++k) {
-        float wk = w[k];
-        float d = ld1(g + k) * hp.gscale + hp.wd * wk;
-        if (mom) {
-          float b = hp.first ? d : hp.momentum * mom[k] + hp.omd * d;
-          mom[k] = b;
-          d = hp.nesterov ? d + hp.momentum * b : b;
-        }
-        wk -= hp.lr * d;
-        w[k] = wk;
-        if (model) st1(model + k, wk);
-      }
+  float* const st[1] = {mom};
+  flat_step<1>(g, w, st, model, n, [&](float gj, float& wj, float& mj) {
+    float d = gj * hp.gscale + hp.wd * wj;
+    if (mom) {
+      float b = hp.first ? d : hp.momentum * mj + hp.omd * d;
+      mj = b;
+      d = hp.nesterov ? d + hp.momentum * b : b;
     }
-  }
+    wj -= hp.lr * d;
+  });
 }
 
 template <typename TG, typename TP>
@@ -294,42 +274,22 @@ __global__ __launch_bounds__(kBlock) void adam_flat_kernel(const TG* __restrict_
                                                             const int* __restrict__ skip) {
   if (skip && *skip) return;
   if (dyn) { hp.lr = dyn[0]; hp.bc1 = dyn[2]; hp.bc2 = dyn[3]; }
-  const int64_t base = (int64_t)blockIdx.x * kChunk;
   const float step = hp.lr / hp.bc1;
   const float rbc2 = 1.f / sqrtf(hp.bc2);
-  for (int64_t i = base + threadIdx.x * kVec; i < base + kChunk; i += kBlock * kVec) {
-    const int cnt = (i + kVec <= n) ? kVec : (i < n ? (int)(n - i) : 0);
-    if (cnt == 0) break;
-    float gv[8], wv[8], mv_[8], vv[8];
-    if (cnt == kVec) {
-      load8(g + i, gv); load8(w + i, wv); load8(m + i, mv_); load8(v + i, vv);
-    } else {
-      for (int j = 0; j < kVec; ++j) {
-        gv[j] = j < cnt ? ld1(g + i + j) : 0.f; wv[j] = j < cnt ? w[i + j] : 0.f;
-        mv_[j] = j < cnt ? m[i + j] : 0.f; vv[j] = j < cnt ? v[i + j] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float gr = gv[j] * hp.gscale;
-      if (!hp.adamw) gr += hp.wd * wv[j];
-      mv_[j] = hp.b1 * mv_[j] + hp.omb1 * gr;
-      vv[j] = hp.b2 * vv[j] + hp.omb2 * gr * gr;
-      if (hp.adamw) wv[j] *= (1.f - hp.lr * hp.wd);
-      // torch: m_hat / (sqrt(v_hat) + eps); Keras/TF: lr*sqrt(bc2)/bc1 * m / (sqrt(v) + eps)
-      float denom = hp.keras_eps ? (sqrtf(vv[j]) + hp.eps) * rbc2 : sqrtf(vv[j]) * rbc2 + hp.eps;
-      wv[j] -= step * mv_[j] / denom;
-    }
-    if (cnt == kVec) {
-      store8(w + i, wv); store8(m + i, mv_); store8(v + i, vv);
-      if (model) store_model(model + i, wv);
-    } else {
-      for (int j = 0; j < cnt; ++j) {
-        w[i + j] = wv[j]; m[i + j] = mv_[j]; v[i + j] = vv[j];
-        if (model) st1(model + i + j, wv[j]);
-      }
-    }
-  }
+  // always given (the binding requires both): with flat_step's null tests left in, the
+  // compiler fuses the m update through the other product in every second lane
+  __builtin_assume(m && v);
+  float* const st[2] = {m, v};
+  flat_step<2>(g, w, st, model, n, [&](float gj, float& wj, float& mj, float& vj) {
+    float gr = gj * hp.gscale;
+    if (!hp.adamw) gr += hp.wd * wj;
+    mj = hp.b1 * mj + hp.omb1 * gr;
+    vj = hp.b2 * vj + hp.omb2 * gr * gr;
+    if (hp.adamw) wj *= (1.f - hp.lr * hp.wd);
+    // torch: m_hat / (sqrt(v_hat) + eps); Keras/TF: lr*sqrt(bc2)/bc1 * m / (sqrt(v) + eps)
+    float denom = hp.keras_eps ? (sqrtf(vj) + hp.eps) * rbc2 : sqrtf(vj) * rbc2 + hp.eps;
+    wj -= step * mj / denom;
+  });
 }
 
 template <typename TG, typename TP>
@@ -343,37 +303,15 @@ __global__ __launch_bounds__(kBlock) void adadelta_flat_kernel(const TG* __restr
                                                                 const int* __restrict__ skip) {
   if (skip && *skip) return;
   if (dyn) hp.lr = dyn[0];
-  const int64_t base = (int64_t)blockIdx.x * kChunk;
-  for (int64_t i = base + threadIdx.x * kVec; i < base + kChunk; i += kBlock * kVec) {
-    const int cnt = (i + kVec <= n) ? kVec : (i < n ? (int)(n - i) : 0);
-    if (cnt == 0) break;
-    float gv[8], wv[8], sv[8], av[8];
-    if (cnt == kVec) {
-      load8(g + i, gv); load8(w + i, wv); load8(sq + i, sv); load8(acc + i, av);
-    } else {
-      for (int j = 0; j < kVec; ++j) {
-        gv[j] = j < cnt ? ld1(g + i + j) : 0.f; wv[j] = j < cnt ? w[i + j] : 0.f;
-        sv[j] = j < cnt ? sq[i + j] : 0.f; av[j] = j < cnt ? acc[i + j] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float gr = gv[j] * hp.gscale + hp.wd * wv[j];
-      sv[j] = hp.rho * sv[j] + hp.omr * gr * gr;
-      float delta = sqrtf(av[j] + hp.eps) / sqrtf(sv[j] + hp.eps) * gr;
-      av[j] = hp.rho * av[j] + hp.omr * delta * delta;
-      wv[j] -= hp.lr * delta;
-    }
-    if (cnt == kVec) {
-      store8(w + i, wv); store8(sq + i, sv); store8(acc + i, av);
-      if (model) store_model(model + i, wv);
-    } else {
-      for (int j = 0; j < cnt; ++j) {
-        w[i + j] = wv[j]; sq[i + j] = sv[j]; acc[i + j] = av[j];
-        if (model) st1(model + i + j, wv[j]);
-      }
-    }
-  }
+  __builtin_assume(sq && acc);   // always given, as in adam_flat_kernel
+  float* const st[2] = {sq, acc};
+  flat_step<2>(g, w, st, model, n, [&](float gj, float& wj, float& sj, float& aj) {
+    float gr = gj * hp.gscale + hp.wd * wj;
+    sj = hp.rho * sj + hp.omr * gr * gr;
+    float delta = sqrtf(aj + hp.eps) / sqrtf(sj + hp.eps) * gr;
+    aj = hp.rho * aj + hp.omr * delta * delta;
+    wj -= hp.lr * delta;
+  });
 }
 
 // ---- segmented reductions (LARS norms, Adasum Gram terms) ----
@@ -747,29 +685,7 @@ __global__ __launch_bounds__(kBlock) void adasum_merge_kernel(const TF* fin, flo
 
 }  // namespace mv
 
-// ---------------- host launchers ----------------
-#define MV_GRID(n) dim3((unsigned)(((n) + kChunk - 1) / kChunk))
-
-#define DISPATCH_GP(gd, md, MACRO)                                  \
-  do {                                                              \
-    if (md == F32) {                                                \
-      using TP = float;                                             \
-      if (gd == F32) { using TG = float; MACRO; }                   \
-      else if (gd == BF16) { using TG = __bf16; MACRO; }            \
-      else { using TG = _Float16; MACRO; }                          \
-    } else if (md == BF16) {                                        \
-      using TP = __bf16;                                            \
-      if (gd == F32) { using TG = float; MACRO; }                   \
-      else if (gd == BF16) { using TG = __bf16; MACRO; }            \
-      else { using TG = _Float16; MACRO; }                          \
-    } else {                                                        \
-      using TP = _Float16;                                          \
-      if (gd == F32) { using TG = float; MACRO; }                   \
-      else if (gd == BF16) { using TG = __bf16; MACRO; }            \
-      else { using TG = _Float16; MACRO; }                          \
-    }                                                               \
-  } while (0)
-
+// ---------------- host launchers (MV_GRID, DISPATCH_GP: mv_flat_step.h) ----------------
 void mv_launch_sgd(const void* g, int gd, float* w, float* mom, void* model, int md, int64_t n,
                    float lr, float momentum, double dampening, float wd, float gscale, int nesterov,
                    int first, const float* dyn, const int* skip, hipStream_t st) {

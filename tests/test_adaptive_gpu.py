@@ -4,6 +4,12 @@ and under DistributedOptimizer, and the Keras classes on a GPU.  The references,
 bounds (c) and the shared cases are in tests/adaptive_reference.py; tests/test_adaptive_cpu.py
 runs the PyTorch fallbacks through the same cases.
 
+Both kernels guard their vector body: RMSprop in a loop of its own, Adagrad through the
+streaming skeleton of csrc/kernels/mv_flat_step.h that the SGD, Adam and Adadelta kernels also
+run on.  test_unaligned[adagrad-*] is the one place that skeleton runs on unaligned operands
+(the bindings of sgd_step / adam_step / adadelta_step refuse them,
+tests/test_bindings_validation.py).
+
 Each test prints its worst err / (2^-24 * mag) next to the counted c."""
 import copy
 

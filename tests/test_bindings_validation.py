@@ -7,8 +7,9 @@ runs before a launch (csrc/kernels/mv_checks.h).
 * GPU tier: a bad *secondary* operand (non-contiguous, wrong dtype, wrong size, other
   device) of an otherwise valid call raises.  Non-contiguous operands are ``base[::2]``
   views and wrong sizes are too large, so every pointer stays inside a live allocation.
-  The flat SGD / Adam / Adadelta steps, whose 16-byte vector body has no scalar fallback,
-  reject a ``base[1:]`` view of any operand before they launch.
+  The flat SGD / Adam / Adadelta steps, which the arenas hand 16-byte-aligned slices only,
+  reject a ``base[1:]`` view of any operand before they launch (their kernels have a
+  one-by-one path for it; the binding keeps the arenas' contract).
 """
 import json
 import os

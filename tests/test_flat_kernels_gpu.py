@@ -6,8 +6,15 @@ paths.  References, counted bounds (c) and the shared cases are in tests/flat_re
 tests/test_flat_reference_cpu.py runs the PyTorch fallbacks through the same cases.
 
 Each test prints its worst err / (2^-24 * mag) next to the counted c.
-No test hands an unaligned pointer to a kernel without a guard (the flat SGD / Adam /
-Adadelta steps: their bindings reject it, tests/test_bindings_validation.py).
+
+Every step kernel guards its vector body: SGD, Adam and Adadelta run on the streaming
+skeleton of csrc/kernels/mv_flat_step.h (as does Adagrad, tests/test_adaptive_gpu.py), which
+sends every element of an unaligned operand through its one-by-one loads and stores; LARS
+guards its own.  The bindings of sgd_step / adam_step / adadelta_step reject an unaligned
+operand all the same (tests/test_bindings_validation.py), so the unaligned branch of the
+skeleton cannot be reached from Python through these three: the same template code is
+exercised unaligned through Adagrad (test_adaptive_gpu.py::test_unaligned), and the guarded
+kernels with bodies of their own through test_unaligned_lars and test_unaligned[rmsprop].
 """
 import pytest
 import torch
@@ -37,7 +44,7 @@ def test_step_dtype_grid(cuda, kind, gdt, mdt):
 
 
 @pytest.mark.parametrize("kind,gdt", [("sgd", f16), ("sgd", bf16), ("lars", f16), ("lars", bf16),
-                                      ("adam", f16), ("adamw", f16)])
+                                      ("adam", f16), ("adamw", f16), ("adadelta", f16)])
 def test_step_sizes(cuda, kind, gdt):
     """the production pairs at every size around a lane (8), a step (2048) and a chunk (4096)"""
     hp, k = None, kind
