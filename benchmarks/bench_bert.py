@@ -4,6 +4,7 @@ with fp16 gradient compression + Adasum through mivod.torch.DistributedOptimizer
 
     python benchmarks/bench_bert.py --steps 20 --warmup 5
     python benchmarks/bench_bert.py --gpus 8          # spawns its own 8 ranks
+    python benchmarks/bench_bert.py --max-grad-norm 1.0   # with global gradient-norm clipping
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
         benchmarks/bench_bert.py --gpus 8
 Prints one JSON line (sequences/sec for the whole job) with a ``comm`` record.
@@ -58,6 +59,8 @@ def main():
     ap.add_argument("--op", default="adasum", choices=["adasum", "average"])
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip the global gradient norm (FusedAdam's max_grad_norm); default off")
     args = ap.parse_args()
     if args.gpus > 1 and not any(k in os.environ for k in ("WORLD_SIZE", "HOROVOD_RANK")):
         sys.path.insert(0, ROOT)
@@ -85,7 +88,8 @@ def main():
     cfg = getattr(BertConfig, args.model)()
     torch.manual_seed(7)
     model = BertForPreTraining(cfg).to(dev).to(torch.bfloat16)
-    opt = FusedAdam(model.parameters(), lr=args.lr, weight_decay=0.01, adamw=True)
+    opt = FusedAdam(model.parameters(), lr=args.lr, weight_decay=0.01, adamw=True,
+                    max_grad_norm=args.max_grad_norm)
     op = hvd.Adasum if args.op == "adasum" else hvd.Average
     opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(),
                                    compression=hvd.Compression.by_name(args.compression), op=op)
@@ -155,7 +159,7 @@ def main():
             "config": {"model": f"BERT-{args.model}", "global_batch": args.batch * size,
                        "seq_len": args.seq, "parallelism": f"dp{size}",
                        "compression": args.compression, "op": args.op,
-                       "optimizer": "mivod FusedAdamW",
+                       "optimizer": "mivod FusedAdamW", "max_grad_norm": args.max_grad_norm,
                        "transport": basics.state().backend if size > 1 else "local"},
             "comm": comm}), flush=True)
     hvd.shutdown()

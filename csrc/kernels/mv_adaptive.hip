@@ -32,8 +32,10 @@ __global__ __launch_bounds__(kBlock) void rmsprop_flat_kernel(const TG* __restri
                                                                TP* __restrict__ model, int64_t n,
                                                                RmspropHp hp,
                                                                const float* __restrict__ dyn,
-                                                               const int* __restrict__ skip) {
+                                                               const int* __restrict__ skip,
+                                                               const float* __restrict__ gclip) {
   if (skip && *skip) return;   // overflow guard: every rank skips this step identically
+  hp.gscale = clipped_gscale(hp.gscale, gclip);   // global-norm clip coefficient (mv_clip.hip)
   if (dyn) hp.lr = dyn[0];
   const bool vec = aligned16(g) && aligned16(w) && aligned16(sq) && aligned16_or_null(ga) &&
                    aligned16_or_null(buf) && aligned16_or_null(model);
@@ -96,8 +98,10 @@ __global__ __launch_bounds__(kBlock) void adagrad_flat_kernel(const TG* __restri
                                                                TP* __restrict__ model, int64_t n,
                                                                AdagradHp hp,
                                                                const float* __restrict__ dyn,
-                                                               const int* __restrict__ skip) {
+                                                               const int* __restrict__ skip,
+                                                               const float* __restrict__ gclip) {
   if (skip && *skip) return;
+  hp.gscale = clipped_gscale(hp.gscale, gclip);
   if (dyn) hp.lr = dyn[0];
   __builtin_assume(sum != nullptr);   // always given: drops flat_step's null tests, as in Adam
   float* const st[1] = {sum};
@@ -114,19 +118,20 @@ __global__ __launch_bounds__(kBlock) void adagrad_flat_kernel(const TG* __restri
 void mv_launch_rmsprop(const void* g, int gd, float* w, float* sq, float* ga, float* buf,
                        void* model, int md, int64_t n, float lr, double alpha, float eps, float wd,
                        float momentum, float gscale, const float* dyn, const int* skip,
-                       hipStream_t st) {
+                       const float* gclip, hipStream_t st) {
   if (n <= 0) return;
   RmspropHp hp{lr, (float)alpha, (float)(1.0 - alpha), eps, wd, gscale, momentum};
   DISPATCH_GP(gd, md, hipLaunchKernelGGL((rmsprop_flat_kernel<TG, TP>), MV_GRID(n), dim3(kBlock), 0,
                                          st, (const TG*)g, w, sq, ga, buf, (TP*)model, n, hp, dyn,
-                                         skip));
+                                         skip, gclip));
 }
 
 void mv_launch_adagrad(const void* g, int gd, float* w, float* sum, void* model, int md, int64_t n,
                        float lr, float eps, float wd, float gscale, const float* dyn,
-                       const int* skip, hipStream_t st) {
+                       const int* skip, const float* gclip, hipStream_t st) {
   if (n <= 0) return;
   AdagradHp hp{lr, eps, wd, gscale};
   DISPATCH_GP(gd, md, hipLaunchKernelGGL((adagrad_flat_kernel<TG, TP>), MV_GRID(n), dim3(kBlock), 0,
-                                         st, (const TG*)g, w, sum, (TP*)model, n, hp, dyn, skip));
+                                         st, (const TG*)g, w, sum, (TP*)model, n, hp, dyn, skip,
+                                         gclip));
 }

@@ -1,7 +1,8 @@
-// mivod._mvk bindings: multi-tensor pack / cast, fused optimizer steps, Adasum (mv_kernels.h,
-// mv_adaptive.h)
+// mivod._mvk bindings: multi-tensor pack / cast, fused optimizer steps, global gradient-norm
+// clipping, Adasum (mv_kernels.h, mv_adaptive.h, mv_clip.h)
 #include "mv_adaptive.h"
 #include "mv_checks.h"
+#include "mv_clip.h"
 #include "mv_kernels.h"
 
 namespace {
@@ -88,17 +89,22 @@ void check_aligned16(const char* fn, const char* what, const void* p) {
 
 // The operands every fused step shares: the flat gradient, the fp32 master weights, the
 // optional low-precision model copy, the device hyperparameter block [lr, first, bc1, bc2]
-// (HIP-graph replays) and the skip flag.
+// (HIP-graph replays), the skip flag and the clip coefficient (given only through the
+// mivod._mvk._clip entry points; the public ones pass none).
 struct StepArgs {
   float* w;
   void* model = nullptr;
   int model_dt = 0;
   const float* dyn;
   const int* skip;
+  const float* gclip;
 };
 
+const OptTensor kNoClip;
+
 StepArgs step_args(const char* fn, const at::Tensor& g, const at::Tensor& w, const OptTensor& model,
-                   const OptTensor& dyn, const OptTensor& skip, bool aligned = true) {
+                   const OptTensor& dyn, const OptTensor& skip, const OptTensor& gclip,
+                   bool aligned = true) {
   check_dense(fn, "grad", g, g);
   if (aligned) check_aligned16(fn, "grad", g.data_ptr());
   StepArgs s;
@@ -113,27 +119,45 @@ StepArgs step_args(const char* fn, const at::Tensor& g, const at::Tensor& w, con
   }
   s.dyn = vec_ptr_opt(fn, "dyn", dyn, g, 4, true);
   s.skip = flag_ptr(fn, "skip", skip, g);
+  s.gclip = vec_ptr_opt(fn, "gclip", gclip, g, 1, true);
   return s;
+}
+
+void sgd_impl(const at::Tensor& g, const at::Tensor& w, const OptTensor& mom,
+              const OptTensor& model, double lr, double momentum, double dampening, double wd,
+              double gscale, bool nesterov, bool first, const OptTensor& dyn,
+              const OptTensor& skip, const OptTensor& gclip) {
+  const StepArgs s = step_args("sgd_step", g, w, model, dyn, skip, gclip);
+  float* mp = vec_ptr_opt("sgd_step", "momentum", mom, g, g.numel());
+  check_aligned16("sgd_step", "momentum", mp);
+  c10::DeviceGuard guard(g.device());
+  mv_launch_sgd(g.data_ptr(), dtype_code(g), s.w, mp, s.model, s.model_dt, g.numel(), (float)lr,
+                (float)momentum, dampening, (float)wd, (float)gscale, nesterov, first,
+                s.dyn, s.skip, s.gclip, cur_stream());
 }
 
 void sgd_step(at::Tensor g, at::Tensor w, c10::optional<at::Tensor> mom,
               c10::optional<at::Tensor> model, double lr, double momentum, double dampening,
               double wd, double gscale, bool nesterov, bool first, c10::optional<at::Tensor> dyn,
               c10::optional<at::Tensor> skip) {
-  const StepArgs s = step_args("sgd_step", g, w, model, dyn, skip);
-  float* mp = vec_ptr_opt("sgd_step", "momentum", mom, g, g.numel());
-  check_aligned16("sgd_step", "momentum", mp);
-  c10::DeviceGuard guard(g.device());
-  mv_launch_sgd(g.data_ptr(), dtype_code(g), s.w, mp, s.model, s.model_dt, g.numel(), (float)lr,
-                (float)momentum, dampening, (float)wd, (float)gscale, nesterov, first,
-                s.dyn, s.skip, cur_stream());
+  sgd_impl(g, w, mom, model, lr, momentum, dampening, wd, gscale, nesterov, first, dyn, skip,
+           kNoClip);
 }
 
-void adam_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
-               c10::optional<at::Tensor> model, double lr, double b1, double b2, double eps,
-               double wd, double gscale, int64_t step, bool adamw, bool keras_eps,
-               c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
-  const StepArgs s = step_args("adam_step", g, w, model, dyn, skip);
+void sgd_step_clip(at::Tensor g, at::Tensor w, c10::optional<at::Tensor> mom,
+                   c10::optional<at::Tensor> model, double lr, double momentum, double dampening,
+                   double wd, double gscale, bool nesterov, bool first,
+                   c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip,
+                   at::Tensor gclip) {
+  sgd_impl(g, w, mom, model, lr, momentum, dampening, wd, gscale, nesterov, first, dyn, skip,
+           gclip);
+}
+
+void adam_impl(const at::Tensor& g, const at::Tensor& w, const at::Tensor& m, const at::Tensor& v,
+               const OptTensor& model, double lr, double b1, double b2, double eps, double wd,
+               double gscale, int64_t step, bool adamw, bool keras_eps, const OptTensor& dyn,
+               const OptTensor& skip, const OptTensor& gclip) {
+  const StepArgs s = step_args("adam_step", g, w, model, dyn, skip, gclip);
   float* mp = vec_ptr("adam_step", "exp_avg", m, g, g.numel());
   float* vp = vec_ptr("adam_step", "exp_avg_sq", v, g, g.numel());
   check_aligned16("adam_step", "exp_avg", mp);
@@ -144,13 +168,31 @@ void adam_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
   c10::DeviceGuard guard(g.device());
   mv_launch_adam(g.data_ptr(), dtype_code(g), s.w, mp, vp, s.model, s.model_dt, g.numel(),
                  (float)lr, b1, b2, (float)eps, (float)wd, (float)gscale, (float)bc1,
-                 (float)bc2, adamw, keras_eps, s.dyn, s.skip, cur_stream());
+                 (float)bc2, adamw, keras_eps, s.dyn, s.skip, s.gclip, cur_stream());
 }
 
-void adadelta_step(at::Tensor g, at::Tensor w, at::Tensor sq, at::Tensor acc,
-                   c10::optional<at::Tensor> model, double lr, double rho, double eps, double wd,
-                   double gscale, c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
-  const StepArgs s = step_args("adadelta_step", g, w, model, dyn, skip);
+void adam_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
+               c10::optional<at::Tensor> model, double lr, double b1, double b2, double eps,
+               double wd, double gscale, int64_t step, bool adamw, bool keras_eps,
+               c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
+  adam_impl(g, w, m, v, model, lr, b1, b2, eps, wd, gscale, step, adamw, keras_eps, dyn, skip,
+            kNoClip);
+}
+
+void adam_step_clip(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
+                    c10::optional<at::Tensor> model, double lr, double b1, double b2, double eps,
+                    double wd, double gscale, int64_t step, bool adamw, bool keras_eps,
+                    c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip,
+                    at::Tensor gclip) {
+  adam_impl(g, w, m, v, model, lr, b1, b2, eps, wd, gscale, step, adamw, keras_eps, dyn, skip,
+            gclip);
+}
+
+void adadelta_impl(const at::Tensor& g, const at::Tensor& w, const at::Tensor& sq,
+                   const at::Tensor& acc, const OptTensor& model, double lr, double rho, double eps,
+                   double wd, double gscale, const OptTensor& dyn, const OptTensor& skip,
+                   const OptTensor& gclip) {
+  const StepArgs s = step_args("adadelta_step", g, w, model, dyn, skip, gclip);
   float* sp = vec_ptr("adadelta_step", "square_avg", sq, g, g.numel());
   float* ap = vec_ptr("adadelta_step", "acc_delta", acc, g, g.numel());
   check_aligned16("adadelta_step", "square_avg", sp);
@@ -158,7 +200,20 @@ void adadelta_step(at::Tensor g, at::Tensor w, at::Tensor sq, at::Tensor acc,
   c10::DeviceGuard guard(g.device());
   mv_launch_adadelta(g.data_ptr(), dtype_code(g), s.w, sp, ap, s.model, s.model_dt, g.numel(),
                      (float)lr, rho, (float)eps, (float)wd, (float)gscale, s.dyn, s.skip,
-                     cur_stream());
+                     s.gclip, cur_stream());
+}
+
+void adadelta_step(at::Tensor g, at::Tensor w, at::Tensor sq, at::Tensor acc,
+                   c10::optional<at::Tensor> model, double lr, double rho, double eps, double wd,
+                   double gscale, c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
+  adadelta_impl(g, w, sq, acc, model, lr, rho, eps, wd, gscale, dyn, skip, kNoClip);
+}
+
+void adadelta_step_clip(at::Tensor g, at::Tensor w, at::Tensor sq, at::Tensor acc,
+                        c10::optional<at::Tensor> model, double lr, double rho, double eps,
+                        double wd, double gscale, c10::optional<at::Tensor> dyn,
+                        c10::optional<at::Tensor> skip, at::Tensor gclip) {
+  adadelta_impl(g, w, sq, acc, model, lr, rho, eps, wd, gscale, dyn, skip, gclip);
 }
 
 // the chunk -> segment tables of the segmented kernels, on `like`'s device
@@ -176,12 +231,13 @@ ChunkTable make_table(const char* fn, const at::Tensor& like, const at::Tensor& 
   return ct;
 }
 
-void lars_step(at::Tensor g, at::Tensor w, at::Tensor mom, c10::optional<at::Tensor> model,
-               at::Tensor cbeg, at::Tensor clen, at::Tensor cseg, at::Tensor seg_c0,
-               at::Tensor seg_nc, at::Tensor sflag, at::Tensor partial, at::Tensor norms, double lr,
-               double momentum, double wd, double eta, double gscale, double eps, bool first,
-               c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
-  const StepArgs s = step_args("lars_step", g, w, model, dyn, skip, false);
+void lars_impl(const at::Tensor& g, const at::Tensor& w, const at::Tensor& mom,
+               const OptTensor& model, const at::Tensor& cbeg, const at::Tensor& clen,
+               const at::Tensor& cseg, const at::Tensor& seg_c0, const at::Tensor& seg_nc,
+               const at::Tensor& sflag, const at::Tensor& partial, const at::Tensor& norms,
+               double lr, double momentum, double wd, double eta, double gscale, double eps,
+               bool first, const OptTensor& dyn, const OptTensor& skip, const OptTensor& gclip) {
+  const StepArgs s = step_args("lars_step", g, w, model, dyn, skip, gclip, false);
   float* mp = vec_ptr("lars_step", "momentum", mom, g, g.numel());
   ChunkTable ct = make_table("lars_step", g, cbeg, clen, cseg, seg_c0, seg_nc);
   int32_t* fp = vec_ptr<int32_t>("lars_step", "sflag", sflag, g, ct.nseg, true);
@@ -190,16 +246,35 @@ void lars_step(at::Tensor g, at::Tensor w, at::Tensor mom, c10::optional<at::Ten
   c10::DeviceGuard guard(g.device());
   mv_launch_lars(g.data_ptr(), dtype_code(g), s.w, mp, s.model, s.model_dt, ct, fp, pp, np,
                  (float)lr, (float)momentum, (float)wd, (float)eta, (float)gscale, (float)eps, first,
-                 s.dyn, s.skip, cur_stream());
+                 s.dyn, s.skip, s.gclip, cur_stream());
 }
 
-void lamb_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
-               c10::optional<at::Tensor> model, at::Tensor cbeg, at::Tensor clen, at::Tensor cseg,
-               at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor sflag, at::Tensor partial,
-               at::Tensor norms, double lr, double b1, double b2, double eps, double wd,
-               double gscale, int64_t step, c10::optional<at::Tensor> dyn,
-               c10::optional<at::Tensor> skip) {
-  const StepArgs s = step_args("lamb_step", g, w, model, dyn, skip, false);
+void lars_step(at::Tensor g, at::Tensor w, at::Tensor mom, c10::optional<at::Tensor> model,
+               at::Tensor cbeg, at::Tensor clen, at::Tensor cseg, at::Tensor seg_c0,
+               at::Tensor seg_nc, at::Tensor sflag, at::Tensor partial, at::Tensor norms, double lr,
+               double momentum, double wd, double eta, double gscale, double eps, bool first,
+               c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
+  lars_impl(g, w, mom, model, cbeg, clen, cseg, seg_c0, seg_nc, sflag, partial, norms, lr,
+            momentum, wd, eta, gscale, eps, first, dyn, skip, kNoClip);
+}
+
+void lars_step_clip(at::Tensor g, at::Tensor w, at::Tensor mom, c10::optional<at::Tensor> model,
+                    at::Tensor cbeg, at::Tensor clen, at::Tensor cseg, at::Tensor seg_c0,
+                    at::Tensor seg_nc, at::Tensor sflag, at::Tensor partial, at::Tensor norms,
+                    double lr, double momentum, double wd, double eta, double gscale, double eps,
+                    bool first, c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip,
+                    at::Tensor gclip) {
+  lars_impl(g, w, mom, model, cbeg, clen, cseg, seg_c0, seg_nc, sflag, partial, norms, lr,
+            momentum, wd, eta, gscale, eps, first, dyn, skip, gclip);
+}
+
+void lamb_impl(const at::Tensor& g, const at::Tensor& w, const at::Tensor& m, const at::Tensor& v,
+               const OptTensor& model, const at::Tensor& cbeg, const at::Tensor& clen,
+               const at::Tensor& cseg, const at::Tensor& seg_c0, const at::Tensor& seg_nc,
+               const at::Tensor& sflag, const at::Tensor& partial, const at::Tensor& norms,
+               double lr, double b1, double b2, double eps, double wd, double gscale, int64_t step,
+               const OptTensor& dyn, const OptTensor& skip, const OptTensor& gclip) {
+  const StepArgs s = step_args("lamb_step", g, w, model, dyn, skip, gclip, false);
   float* mp = vec_ptr("lamb_step", "exp_avg", m, g, g.numel());
   float* vp = vec_ptr("lamb_step", "exp_avg_sq", v, g, g.numel());
   ChunkTable ct = make_table("lamb_step", g, cbeg, clen, cseg, seg_c0, seg_nc);
@@ -212,15 +287,36 @@ void lamb_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
   c10::DeviceGuard guard(g.device());
   mv_launch_lamb(g.data_ptr(), dtype_code(g), s.w, mp, vp, s.model, s.model_dt, ct, fp, pp, np,
                  (float)lr, b1, b2, (float)eps, (float)wd, (float)gscale, (float)bc1, (float)bc2,
-                 s.dyn, s.skip, cur_stream());
+                 s.dyn, s.skip, s.gclip, cur_stream());
+}
+
+void lamb_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
+               c10::optional<at::Tensor> model, at::Tensor cbeg, at::Tensor clen, at::Tensor cseg,
+               at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor sflag, at::Tensor partial,
+               at::Tensor norms, double lr, double b1, double b2, double eps, double wd,
+               double gscale, int64_t step, c10::optional<at::Tensor> dyn,
+               c10::optional<at::Tensor> skip) {
+  lamb_impl(g, w, m, v, model, cbeg, clen, cseg, seg_c0, seg_nc, sflag, partial, norms, lr, b1, b2,
+            eps, wd, gscale, step, dyn, skip, kNoClip);
+}
+
+void lamb_step_clip(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
+                    c10::optional<at::Tensor> model, at::Tensor cbeg, at::Tensor clen,
+                    at::Tensor cseg, at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor sflag,
+                    at::Tensor partial, at::Tensor norms, double lr, double b1, double b2,
+                    double eps, double wd, double gscale, int64_t step,
+                    c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip,
+                    at::Tensor gclip) {
+  lamb_impl(g, w, m, v, model, cbeg, clen, cseg, seg_c0, seg_nc, sflag, partial, norms, lr, b1, b2,
+            eps, wd, gscale, step, dyn, skip, gclip);
 }
 
 // RMSprop / Adagrad (mv_adaptive.hip).  grad_avg given: centered; momentum_buffer given: momentum.
-void rmsprop_step(at::Tensor g, at::Tensor w, at::Tensor sq, c10::optional<at::Tensor> ga,
-                  c10::optional<at::Tensor> buf, c10::optional<at::Tensor> model, double lr,
+void rmsprop_impl(const at::Tensor& g, const at::Tensor& w, const at::Tensor& sq,
+                  const OptTensor& ga, const OptTensor& buf, const OptTensor& model, double lr,
                   double alpha, double eps, double wd, double momentum, double gscale,
-                  c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
-  const StepArgs s = step_args("rmsprop_step", g, w, model, dyn, skip, false);
+                  const OptTensor& dyn, const OptTensor& skip, const OptTensor& gclip) {
+  const StepArgs s = step_args("rmsprop_step", g, w, model, dyn, skip, gclip, false);
   float* sp = vec_ptr("rmsprop_step", "square_avg", sq, g, g.numel());
   float* gp = vec_ptr_opt("rmsprop_step", "grad_avg", ga, g, g.numel());
   float* bp = vec_ptr_opt("rmsprop_step", "momentum_buffer", buf, g, g.numel());
@@ -229,17 +325,66 @@ void rmsprop_step(at::Tensor g, at::Tensor w, at::Tensor sq, c10::optional<at::T
   c10::DeviceGuard guard(g.device());
   mv_launch_rmsprop(g.data_ptr(), dtype_code(g), s.w, sp, gp, bp, s.model, s.model_dt, g.numel(),
                     (float)lr, alpha, (float)eps, (float)wd, (float)momentum, (float)gscale, s.dyn,
-                    s.skip, cur_stream());
+                    s.skip, s.gclip, cur_stream());
+}
+
+void rmsprop_step(at::Tensor g, at::Tensor w, at::Tensor sq, c10::optional<at::Tensor> ga,
+                  c10::optional<at::Tensor> buf, c10::optional<at::Tensor> model, double lr,
+                  double alpha, double eps, double wd, double momentum, double gscale,
+                  c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip) {
+  rmsprop_impl(g, w, sq, ga, buf, model, lr, alpha, eps, wd, momentum, gscale, dyn, skip, kNoClip);
+}
+
+void rmsprop_step_clip(at::Tensor g, at::Tensor w, at::Tensor sq, c10::optional<at::Tensor> ga,
+                       c10::optional<at::Tensor> buf, c10::optional<at::Tensor> model, double lr,
+                       double alpha, double eps, double wd, double momentum, double gscale,
+                       c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip,
+                       at::Tensor gclip) {
+  rmsprop_impl(g, w, sq, ga, buf, model, lr, alpha, eps, wd, momentum, gscale, dyn, skip, gclip);
+}
+
+void adagrad_impl(const at::Tensor& g, const at::Tensor& w, const at::Tensor& sum,
+                  const OptTensor& model, double lr, double eps, double wd, double gscale,
+                  const OptTensor& dyn, const OptTensor& skip, const OptTensor& gclip) {
+  const StepArgs s = step_args("adagrad_step", g, w, model, dyn, skip, gclip, false);
+  float* sp = vec_ptr("adagrad_step", "sum", sum, g, g.numel());
+  c10::DeviceGuard guard(g.device());
+  mv_launch_adagrad(g.data_ptr(), dtype_code(g), s.w, sp, s.model, s.model_dt, g.numel(),
+                    (float)lr, (float)eps, (float)wd, (float)gscale, s.dyn, s.skip, s.gclip,
+                    cur_stream());
 }
 
 void adagrad_step(at::Tensor g, at::Tensor w, at::Tensor sum, c10::optional<at::Tensor> model,
                   double lr, double eps, double wd, double gscale, c10::optional<at::Tensor> dyn,
                   c10::optional<at::Tensor> skip) {
-  const StepArgs s = step_args("adagrad_step", g, w, model, dyn, skip, false);
-  float* sp = vec_ptr("adagrad_step", "sum", sum, g, g.numel());
-  c10::DeviceGuard guard(g.device());
-  mv_launch_adagrad(g.data_ptr(), dtype_code(g), s.w, sp, s.model, s.model_dt, g.numel(),
-                    (float)lr, (float)eps, (float)wd, (float)gscale, s.dyn, s.skip, cur_stream());
+  adagrad_impl(g, w, sum, model, lr, eps, wd, gscale, dyn, skip, kNoClip);
+}
+
+void adagrad_step_clip(at::Tensor g, at::Tensor w, at::Tensor sum, c10::optional<at::Tensor> model,
+                       double lr, double eps, double wd, double gscale,
+                       c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip,
+                       at::Tensor gclip) {
+  adagrad_impl(g, w, sum, model, lr, eps, wd, gscale, dyn, skip, gclip);
+}
+
+// Global gradient-norm clipping (mv_clip.hip).  grad_sumsq writes one fp32 partial per
+// 4096-element chunk of x; clip_finalize turns partial[0:total) into clip = [coef, norm].
+void grad_sumsq(at::Tensor x, at::Tensor partial, c10::optional<at::Tensor> flag) {
+  check_dense("grad_sumsq", "x", x, x);
+  const int64_t nchunks = (x.numel() + kChunk - 1) / kChunk;
+  float* pp = vec_ptr("grad_sumsq", "partial", partial, x, nchunks, true);
+  int* fp = flag_ptr("grad_sumsq", "flag", flag, x);
+  c10::DeviceGuard guard(x.device());
+  mv_launch_grad_sumsq(x.data_ptr(), dtype_code(x), x.numel(), pp, fp, cur_stream());
+}
+
+void clip_finalize(at::Tensor partial, int64_t total, double gscale, double max_norm,
+                   at::Tensor clip) {
+  TORCH_CHECK(total >= 0, "clip_finalize: total must be >= 0");
+  const float* pp = vec_ptr("clip_finalize", "partial", partial, partial, total, true);
+  float* cp = vec_ptr("clip_finalize", "clip", clip, partial, 2, true);
+  c10::DeviceGuard guard(partial.device());
+  mv_launch_clip_finalize(pp, total, gscale, max_norm, cp, cur_stream());
 }
 
 void seg_dot3(at::Tensor a, at::Tensor b, at::Tensor cbeg, at::Tensor clen, at::Tensor cseg,
@@ -333,6 +478,22 @@ void bind_optim(pybind11::module_& m) {
       "_adaptive", "RMSprop and Adagrad steps on the flat-arena path");
   ad.def("rmsprop_step", &rmsprop_step, "fused flat RMSprop step (centered / momentum optional)");
   ad.def("adagrad_step", &adagrad_step, "fused flat Adagrad step");
+  // and global gradient-norm clipping: mivod._mvk._clip, the norm kernels and every step with
+  // the device clip coefficient as one more trailing operand
+  pybind11::module_ cl = m.def_submodule(
+      "_clip", "global gradient-norm clipping (max_grad_norm) on the flat-arena path");
+  cl.def("grad_sumsq", &grad_sumsq,
+         "partial[b] = fp32 sum of squares of chunk b (deterministic); flag |= any non-finite");
+  cl.def("clip_finalize", &clip_finalize,
+         "clip = [min(1, max_norm / (norm + 1e-6)), norm], norm = gscale * sqrt(sum partial)");
+  cl.def("sgd_step", &sgd_step_clip, "sgd_step with gscale *= gclip[0] on the device");
+  cl.def("adam_step", &adam_step_clip, "adam_step with gscale *= gclip[0] on the device");
+  cl.def("adadelta_step", &adadelta_step_clip,
+         "adadelta_step with gscale *= gclip[0] on the device");
+  cl.def("lars_step", &lars_step_clip, "lars_step with gscale *= gclip[0] on the device");
+  cl.def("lamb_step", &lamb_step_clip, "lamb_step with gscale *= gclip[0] on the device");
+  cl.def("rmsprop_step", &rmsprop_step_clip, "rmsprop_step with gscale *= gclip[0] on the device");
+  cl.def("adagrad_step", &adagrad_step_clip, "adagrad_step with gscale *= gclip[0] on the device");
   m.def("seg_dot3", &seg_dot3, "per-segment (a.b, |a|^2, |b|^2) (swap: (a.b, |b|^2, |a|^2))");
   m.def("adasum_merge", &adasum_merge,
         "one vector-halving Adasum level: merge with fixed-order group Gram sums + fused wire cast");

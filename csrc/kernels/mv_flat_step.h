@@ -9,6 +9,19 @@
 
 namespace mv {
 
+// gscale under the nullable device clip coefficient of global gradient-norm clipping
+// (mv_clip.hip): one fp32 product, taken once per thread before the element loop, so a
+// clipped launch is the unclipped launch of gscale * gclip[0] bit for bit.  The product is
+// uniform and goes back into a scalar register, where the element loop found gscale before
+// the operand existed: left in a vector register it cost every instantiation two VGPRs
+// (rmsprop_flat_kernel reached 80, the edge of its occupancy step).  Either way the operand
+// moves registers around, which is enough to change the product that -ffp-contract=fast fuses
+// in an a*b + c*d (sgd_flat_kernel spells its one out for that reason).
+__device__ __forceinline__ float clipped_gscale(float gscale, const float* __restrict__ gclip) {
+  if (!gclip) return gscale;
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(gscale * *gclip)));
+}
+
 // f(g, w, s0, .., s{NS-1}) on element j of the registers.  The state reaches f as NS references
 // into sv, not as a float (&)[NS] gathered from it and scattered back: the copies change the
 // register allocation (RMSprop's arithmetic on this loop: 104-114 VGPRs with them, 72-84

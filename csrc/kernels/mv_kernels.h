@@ -33,24 +33,29 @@ void mv_launch_flat_cast(const void* src, int sd, void* dst, int dd, int64_t n, 
 // dampening, b1, b2 and rho arrive as doubles: their complements 1 - x are rounded to fp32 once
 void mv_launch_sgd(const void* g, int gd, float* w, float* mom, void* model, int md, int64_t n,
                    float lr, float momentum, double dampening, float wd, float gscale, int nesterov,
-                   int first, const float* dyn, const int* skip, hipStream_t st);
+                   int first, const float* dyn, const int* skip, const float* gclip,
+                   hipStream_t st);
 // skip (nullable): device int32; nonzero => the kernel returns without updating
 // (fp16-wire overflow guard, identical on every rank after the flag allreduce)
 // dyn (nullable): device [lr, first, bc1, bc2] read by the kernel instead of the
 // scalar arguments — HIP-graph replayable hyperparameters (mivod/torch/graphs.py)
+// gclip (nullable): device fp32 clip coefficient of the step (mv_clip.h); the kernel
+// multiplies gscale by gclip[0], one fp32 product, before any element is touched (LARS: in
+// both the norm pass and the update, so the trust ratio sees the clipped gradient)
 // m, v (Adam) and sq, acc (Adadelta) must not be null: the kernels tell the compiler so
 // (__builtin_assume), and a null one is undefined behaviour, not a skipped stream
 void mv_launch_adam(const void* g, int gd, float* w, float* m, float* v, void* model, int md,
                     int64_t n, float lr, double b1, double b2, float eps, float wd, float gscale,
                     float bc1, float bc2, int adamw, int keras_eps, const float* dyn,
-                    const int* skip, hipStream_t st);
+                    const int* skip, const float* gclip, hipStream_t st);
 void mv_launch_adadelta(const void* g, int gd, float* w, float* sq, float* acc, void* model, int md,
                         int64_t n, float lr, double rho, float eps, float wd, float gscale,
-                        const float* dyn, const int* skip, hipStream_t st);
+                        const float* dyn, const int* skip, const float* gclip, hipStream_t st);
 void mv_launch_lars(const void* g, int gd, float* w, float* mom, void* model, int md,
                     const ChunkTable& ct, const int32_t* sflag, float* partial, float* norms,
                     float lr, float momentum, float wd, float eta, float gscale, float eps,
-                    int first, const float* dyn, const int* skip, hipStream_t st);
+                    int first, const float* dyn, const int* skip, const float* gclip,
+                    hipStream_t st);
 // LAMB: m, v updated and per-chunk (|w|^2, |u|^2) partials, the segment reduce into
 // norms[2 * nseg], then w -= lr * trust * u with u recomputed from the stored m, v and w.
 // sflag bit0: the segment takes no weight decay and trust 1.  dyn overrides lr, bc1, bc2;
@@ -58,7 +63,8 @@ void mv_launch_lars(const void* g, int gd, float* w, float* mom, void* model, in
 void mv_launch_lamb(const void* g, int gd, float* w, float* m, float* v, void* model, int md,
                     const ChunkTable& ct, const int32_t* sflag, float* partial, float* norms,
                     float lr, double b1, double b2, float eps, float wd, float gscale, float bc1,
-                    float bc2, const float* dyn, const int* skip, hipStream_t st);
+                    float bc2, const float* dyn, const int* skip, const float* gclip,
+                    hipStream_t st);
 // swap: store (a.b, |b|^2, |a|^2) (the Adasum level kernels, f holding b)
 void mv_launch_seg_dot3(const void* a, const void* b, int dt, const ChunkTable& ct, float* partial,
                         float* out, int swap, hipStream_t st);

@@ -248,12 +248,18 @@ __global__ __launch_bounds__(kBlock) void sgd_flat_kernel(const TG* __restrict__
                                                            TP* __restrict__ model, int64_t n,
                                                            SgdHp hp,
                                                            const float* __restrict__ dyn,
-                                                           const int* __restrict__ skip) {
+                                                           const int* __restrict__ skip,
+                                                           const float* __restrict__ gclip) {
   if (skip && *skip) return;   // overflow guard: every rank skips this step identically
+  hp.gscale = clipped_gscale(hp.gscale, gclip);
   if (dyn) { hp.lr = dyn[0]; hp.first = dyn[1] != 0.f; }
   float* const st[1] = {mom};
   flat_step<1>(g, w, st, model, n, [&](float gj, float& wj, float& mj) {
-    float d = gj * hp.gscale + hp.wd * wj;
+    // g*gscale rounded, wd*w fused into the add: spelled out, because which product of
+    // a*b + c*d -ffp-contract=fast fuses here follows the registers the two scales happen to
+    // live in (with the gclip operand added the compiler fused the other one, and every
+    // result of a step with weight decay moved by a rounding)
+    float d = __builtin_fmaf(hp.wd, wj, gj * hp.gscale);
     if (mom) {
       float b = hp.first ? d : hp.momentum * mj + hp.omd * d;
       mj = b;
@@ -271,8 +277,10 @@ __global__ __launch_bounds__(kBlock) void adam_flat_kernel(const TG* __restrict_
                                                             TP* __restrict__ model, int64_t n,
                                                             AdamHp hp,
                                                             const float* __restrict__ dyn,
-                                                            const int* __restrict__ skip) {
+                                                            const int* __restrict__ skip,
+                                                            const float* __restrict__ gclip) {
   if (skip && *skip) return;
+  hp.gscale = clipped_gscale(hp.gscale, gclip);
   if (dyn) { hp.lr = dyn[0]; hp.bc1 = dyn[2]; hp.bc2 = dyn[3]; }
   const float step = hp.lr / hp.bc1;
   const float rbc2 = 1.f / sqrtf(hp.bc2);
@@ -300,8 +308,10 @@ __global__ __launch_bounds__(kBlock) void adadelta_flat_kernel(const TG* __restr
                                                                 TP* __restrict__ model, int64_t n,
                                                                 AdadeltaHp hp,
                                                                 const float* __restrict__ dyn,
-                                                                const int* __restrict__ skip) {
+                                                                const int* __restrict__ skip,
+                                                                const float* __restrict__ gclip) {
   if (skip && *skip) return;
+  hp.gscale = clipped_gscale(hp.gscale, gclip);
   if (dyn) hp.lr = dyn[0];
   __builtin_assume(sq && acc);   // always given, as in adam_flat_kernel
   float* const st[2] = {sq, acc};
@@ -325,8 +335,10 @@ __global__ __launch_bounds__(kBlock) void seg_partial_kernel(const TA* __restric
                                                               const int64_t* __restrict__ cbeg,
                                                               const int32_t* __restrict__ clen,
                                                               float* __restrict__ partial,
-                                                              float bscale) {
+                                                              float bscale,
+                                                              const float* __restrict__ gclip) {
   constexpr int NV = MODE == 0 ? 2 : 3;
+  bscale = clipped_gscale(bscale, gclip);   // LARS measures the norm of the clipped gradient
   const int c = blockIdx.x;
   const int64_t beg = cbeg[c];
   const int len = clen[c];
@@ -402,8 +414,10 @@ __global__ __launch_bounds__(kBlock) void lars_flat_kernel(const TG* __restrict_
                                                             const float* __restrict__ norms,
                                                             LarsHp hp,
                                                             const float* __restrict__ dyn,
-                                                            const int* __restrict__ skip) {
+                                                            const int* __restrict__ skip,
+                                                            const float* __restrict__ gclip) {
   if (skip && *skip) return;
+  hp.gscale = clipped_gscale(hp.gscale, gclip);
   if (dyn) { hp.lr = dyn[0]; hp.first = dyn[1] != 0.f; }
   const int c = blockIdx.x;
   const int64_t beg = cbeg[c];
@@ -479,8 +493,10 @@ __global__ __launch_bounds__(kBlock) void lamb_moments_kernel(const TG* __restri
                                                                float* __restrict__ partial,
                                                                LambHp hp,
                                                                const float* __restrict__ dyn,
-                                                               const int* __restrict__ skip) {
+                                                               const int* __restrict__ skip,
+                                                               const float* __restrict__ gclip) {
   if (skip && *skip) return;   // uniform: no lane reaches block_sum's barrier
+  hp.gscale = clipped_gscale(hp.gscale, gclip);
   if (dyn) { hp.bc1 = dyn[2]; hp.bc2 = dyn[3]; }
   const int c = blockIdx.x;
   const int64_t beg = cbeg[c];
@@ -688,58 +704,63 @@ __global__ __launch_bounds__(kBlock) void adasum_merge_kernel(const TF* fin, flo
 // ---------------- host launchers (MV_GRID, DISPATCH_GP: mv_flat_step.h) ----------------
 void mv_launch_sgd(const void* g, int gd, float* w, float* mom, void* model, int md, int64_t n,
                    float lr, float momentum, double dampening, float wd, float gscale, int nesterov,
-                   int first, const float* dyn, const int* skip, hipStream_t st) {
+                   int first, const float* dyn, const int* skip, const float* gclip,
+                   hipStream_t st) {
   if (n <= 0) return;
   SgdHp hp{lr, momentum, (float)(1.0 - dampening), wd, gscale, nesterov, first};
   DISPATCH_GP(gd, md, hipLaunchKernelGGL((sgd_flat_kernel<TG, TP>), MV_GRID(n), dim3(kBlock), 0,
-                                         st, (const TG*)g, w, mom, (TP*)model, n, hp, dyn, skip));
+                                         st, (const TG*)g, w, mom, (TP*)model, n, hp, dyn, skip,
+                                         gclip));
 }
 
 void mv_launch_adam(const void* g, int gd, float* w, float* m, float* v, void* model, int md,
                     int64_t n, float lr, double b1, double b2, float eps, float wd, float gscale,
                     float bc1, float bc2, int adamw, int keras_eps, const float* dyn,
-                    const int* skip, hipStream_t st) {
+                    const int* skip, const float* gclip, hipStream_t st) {
   if (n <= 0) return;
   AdamHp hp{lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), eps, wd, gscale,
             bc1, bc2, adamw, keras_eps};
   DISPATCH_GP(gd, md, hipLaunchKernelGGL((adam_flat_kernel<TG, TP>), MV_GRID(n), dim3(kBlock), 0,
-                                         st, (const TG*)g, w, m, v, (TP*)model, n, hp, dyn, skip));
+                                         st, (const TG*)g, w, m, v, (TP*)model, n, hp, dyn, skip,
+                                         gclip));
 }
 
 void mv_launch_adadelta(const void* g, int gd, float* w, float* sq, float* acc, void* model,
                         int md, int64_t n, float lr, double rho, float eps, float wd, float gscale,
-                        const float* dyn, const int* skip, hipStream_t st) {
+                        const float* dyn, const int* skip, const float* gclip, hipStream_t st) {
   if (n <= 0) return;
   AdadeltaHp hp{lr, (float)rho, (float)(1.0 - rho), eps, wd, gscale};
   DISPATCH_GP(gd, md, hipLaunchKernelGGL((adadelta_flat_kernel<TG, TP>), MV_GRID(n), dim3(kBlock),
                                          0, st, (const TG*)g, w, sq, acc, (TP*)model, n, hp, dyn,
-                                         skip));
+                                         skip, gclip));
 }
 
 void mv_launch_lars(const void* g, int gd, float* w, float* mom, void* model, int md,
                     const ChunkTable& ct, const int32_t* sflag, float* partial, float* norms,
                     float lr, float momentum, float wd, float eta, float gscale, float eps,
-                    int first, const float* dyn, const int* skip, hipStream_t st) {
+                    int first, const float* dyn, const int* skip, const float* gclip,
+                    hipStream_t st) {
   if (ct.nchunks <= 0) return;
   // pass 1: per-chunk (|w|^2, |g|^2)
   switch (gd) {
-    case F32: hipLaunchKernelGGL((seg_partial_kernel<float, float, 0>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const float*)w, (const float*)g, ct.begin, ct.len, partial, gscale); break;
-    case BF16: hipLaunchKernelGGL((seg_partial_kernel<float, __bf16, 0>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const float*)w, (const __bf16*)g, ct.begin, ct.len, partial, gscale); break;
-    case F16: hipLaunchKernelGGL((seg_partial_kernel<float, _Float16, 0>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const float*)w, (const _Float16*)g, ct.begin, ct.len, partial, gscale); break;
+    case F32: hipLaunchKernelGGL((seg_partial_kernel<float, float, 0>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const float*)w, (const float*)g, ct.begin, ct.len, partial, gscale, gclip); break;
+    case BF16: hipLaunchKernelGGL((seg_partial_kernel<float, __bf16, 0>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const float*)w, (const __bf16*)g, ct.begin, ct.len, partial, gscale, gclip); break;
+    case F16: hipLaunchKernelGGL((seg_partial_kernel<float, _Float16, 0>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const float*)w, (const _Float16*)g, ct.begin, ct.len, partial, gscale, gclip); break;
   }
   hipLaunchKernelGGL((seg_reduce_kernel<2>), dim3(ct.nseg), dim3(kWave), 0, st, partial, ct.seg_c0,
                      ct.seg_nc, norms, 0);
-  // norms[2s+1] already includes gscale (bscale in pass 1)
+  // norms[2s+1] already includes gscale (bscale in pass 1) and the clip coefficient
   LarsHp hp{lr, momentum, wd, eta, gscale, eps, first};
   DISPATCH_GP(gd, md, hipLaunchKernelGGL((lars_flat_kernel<TG, TP>), dim3(ct.nchunks), dim3(kBlock),
                                          0, st, (const TG*)g, w, mom, (TP*)model, ct.begin, ct.len,
-                                         ct.seg, sflag, norms, hp, dyn, skip));
+                                         ct.seg, sflag, norms, hp, dyn, skip, gclip));
 }
 
 void mv_launch_lamb(const void* g, int gd, float* w, float* m, float* v, void* model, int md,
                     const ChunkTable& ct, const int32_t* sflag, float* partial, float* norms,
                     float lr, double b1, double b2, float eps, float wd, float gscale, float bc1,
-                    float bc2, const float* dyn, const int* skip, hipStream_t st) {
+                    float bc2, const float* dyn, const int* skip, const float* gclip,
+                    hipStream_t st) {
   if (ct.nchunks <= 0) return;
   LambHp hp{lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), eps, wd, gscale,
             bc1, bc2};
@@ -747,7 +768,7 @@ void mv_launch_lamb(const void* g, int gd, float* w, float* m, float* v, void* m
 #define MV_LAMB1(TG)                                                                            \
   hipLaunchKernelGGL((lamb_moments_kernel<TG>), dim3(ct.nchunks), dim3(kBlock), 0, st,           \
                      (const TG*)g, (const float*)w, m, v, ct.begin, ct.len, ct.seg, sflag,       \
-                     partial, hp, dyn, skip)
+                     partial, hp, dyn, skip, gclip)
   switch (gd) {
     case F32: MV_LAMB1(float); break;
     case BF16: MV_LAMB1(__bf16); break;
@@ -773,9 +794,9 @@ void mv_launch_seg_dot3(const void* a, const void* b, int dt, const ChunkTable& 
                         float* out, int swap, hipStream_t st) {
   if (ct.nchunks <= 0) return;
   switch (dt) {
-    case F32: hipLaunchKernelGGL((seg_partial_kernel<float, float, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const float*)a, (const float*)b, ct.begin, ct.len, partial, 1.f); break;
-    case BF16: hipLaunchKernelGGL((seg_partial_kernel<__bf16, __bf16, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const __bf16*)a, (const __bf16*)b, ct.begin, ct.len, partial, 1.f); break;
-    case F16: hipLaunchKernelGGL((seg_partial_kernel<_Float16, _Float16, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const _Float16*)a, (const _Float16*)b, ct.begin, ct.len, partial, 1.f); break;
+    case F32: hipLaunchKernelGGL((seg_partial_kernel<float, float, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const float*)a, (const float*)b, ct.begin, ct.len, partial, 1.f, nullptr); break;
+    case BF16: hipLaunchKernelGGL((seg_partial_kernel<__bf16, __bf16, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const __bf16*)a, (const __bf16*)b, ct.begin, ct.len, partial, 1.f, nullptr); break;
+    case F16: hipLaunchKernelGGL((seg_partial_kernel<_Float16, _Float16, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, (const _Float16*)a, (const _Float16*)b, ct.begin, ct.len, partial, 1.f, nullptr); break;
   }
   hipLaunchKernelGGL((seg_reduce_kernel<3>), dim3(ct.nseg), dim3(kWave), 0, st, partial, ct.seg_c0,
                      ct.seg_nc, out, swap);
@@ -785,9 +806,9 @@ void mv_launch_seg_dot3_f(const float* a, const void* b, int bdt, const ChunkTab
                           float* partial, float* out, int swap, hipStream_t st) {
   if (ct.nchunks <= 0) return;
   switch (bdt) {
-    case F32: hipLaunchKernelGGL((seg_partial_kernel<float, float, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, a, (const float*)b, ct.begin, ct.len, partial, 1.f); break;
-    case BF16: hipLaunchKernelGGL((seg_partial_kernel<float, __bf16, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, a, (const __bf16*)b, ct.begin, ct.len, partial, 1.f); break;
-    case F16: hipLaunchKernelGGL((seg_partial_kernel<float, _Float16, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, a, (const _Float16*)b, ct.begin, ct.len, partial, 1.f); break;
+    case F32: hipLaunchKernelGGL((seg_partial_kernel<float, float, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, a, (const float*)b, ct.begin, ct.len, partial, 1.f, nullptr); break;
+    case BF16: hipLaunchKernelGGL((seg_partial_kernel<float, __bf16, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, a, (const __bf16*)b, ct.begin, ct.len, partial, 1.f, nullptr); break;
+    case F16: hipLaunchKernelGGL((seg_partial_kernel<float, _Float16, 1>), dim3(ct.nchunks), dim3(kBlock), 0, st, a, (const _Float16*)b, ct.begin, ct.len, partial, 1.f, nullptr); break;
   }
   hipLaunchKernelGGL((seg_reduce_kernel<3>), dim3(ct.nseg), dim3(kWave), 0, st, partial, ct.seg_c0,
                      ct.seg_nc, out, swap);

@@ -125,6 +125,92 @@ def nonfinite_scan(x: torch.Tensor, flag: torch.Tensor) -> None:
 
 
 # ---------------------------------------------------------------------------
+# Global gradient-norm clipping (max_grad_norm of the Fused* optimizers)
+# ---------------------------------------------------------------------------
+def sumsq_chunks(n: int) -> int:
+    """Entries of ``partial`` that ``grad_sumsq`` writes for ``n`` elements."""
+    return (int(n) + CHUNK - 1) // CHUNK
+
+
+def grad_sumsq(x: torch.Tensor, partial: torch.Tensor, flag: Optional[torch.Tensor] = None) -> None:
+    """partial[b] = fp32 sum of squares of x[b*4096 : (b+1)*4096] for every chunk b of the
+    flat bucket ``x`` (written, not accumulated; entries past the last chunk stay), reduced in
+    a fixed order so that equal inputs give equal bits.  ``flag`` (optional) |= any non-finite
+    element of ``x``, as ``nonfinite_scan``: the overflow guard's scan and the norm share one
+    read-only pass."""
+    n, nc = x.numel(), sumsq_chunks(x.numel())
+    if _on_gpu(x):
+        native()._clip.grad_sumsq(x, partial, flag)
+        return
+    if partial.dtype != torch.float32 or partial.numel() < nc:
+        raise ValueError(f"grad_sumsq: partial must hold at least {nc} fp32 entries")
+    if n == 0:
+        return
+    # the kernel's summation structure (csrc/kernels/mv_clip.hip): lane t of 256 adds its 8
+    # consecutive elements of step 0, then of step 1; the 64-lane butterfly; the 4 waves in
+    # order.  Zeros pad the last chunk (adding them is exact).
+    v = torch.zeros(nc * CHUNK, dtype=torch.float32)
+    v[:n] = x.reshape(-1).float()
+    if flag is not None and not bool(torch.isfinite(v).all()):
+        flag.fill_(1)
+    sq = (v * v).view(nc, 2, 256, 8)
+    acc = torch.zeros(nc, 256, dtype=torch.float32)
+    for s in range(2):
+        for j in range(8):
+            acc = acc + sq[:, s, :, j]
+    acc = acc.view(nc, 4, 64)
+    lane = torch.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, :, lane ^ o]
+    tot = torch.zeros(nc, dtype=torch.float32)
+    for w in range(4):
+        tot = tot + acc[:, w, 0]
+    partial[:nc].copy_(tot)
+
+
+def clip_finalize(partial: torch.Tensor, total: int, clip: torch.Tensor, *, gscale: float,
+                  max_norm: float) -> None:
+    """clip[0] = min(1, max_norm / (norm + 1e-6)) and clip[1] = norm = gscale *
+    sqrt(sum(partial[:total])) (torch.nn.utils.clip_grad_norm_'s coefficient), the sum, the
+    root and the quotient in float64 and in a fixed order, each result rounded to fp32 once.
+    A non-finite sum gives clip[0] = NaN (never a finite coefficient from a norm that is
+    not)."""
+    total = int(total)
+    if _on_gpu(partial):
+        native()._clip.clip_finalize(partial, total, float(gscale), float(max_norm), clip)
+        return
+    if total < 0 or partial.numel() < total or clip.numel() < 2:
+        raise ValueError("clip_finalize: partial must hold total entries and clip 2")
+    rows = max((total + 255) // 256, 1)
+    p = torch.zeros(rows * 256, dtype=torch.float64)
+    p[:total] = partial[:total].double()
+    s = torch.zeros(256, dtype=torch.float64)
+    for r in p.view(rows, 256):            # lane t adds partial[t], partial[t + 256], ..
+        s = s + r
+    h = 128
+    while h:                               # the binary tree over the 256 lanes
+        s = s[:h] + s[h:2 * h]
+        h //= 2
+    tot = float(s[0])
+    norm = float(gscale) * math.sqrt(tot) if tot == tot else tot
+    if math.isfinite(tot):
+        q = float(max_norm) / (norm + 1e-6)
+        coef = 1.0 if q > 1.0 else q
+    else:
+        coef = math.nan
+    clip[0] = coef
+    clip[1] = norm
+
+
+def _clipped(gscale: float, gclip) -> float:
+    """The fallbacks' gscale under a clip coefficient: fp32(gscale) * fp32(gclip[0]) rounded to
+    fp32, the one product the kernels take."""
+    if gclip is None:
+        return gscale
+    return float(torch.tensor(float(gscale), dtype=torch.float32) * gclip.reshape(-1)[0].float())
+
+
+# ---------------------------------------------------------------------------
 # K6 fused optimizers (flat)
 # ---------------------------------------------------------------------------
 def _skipped(skip) -> bool:
@@ -132,17 +218,23 @@ def _skipped(skip) -> bool:
 
 
 def sgd_step(g, w, mom, model, *, lr, momentum=0.0, dampening=0.0, weight_decay=0.0,
-             gscale=1.0, nesterov=False, first=False, dyn=None, skip=None):
+             gscale=1.0, nesterov=False, first=False, dyn=None, skip=None, gclip=None):
     """``dyn`` (GPU only): device fp32 [lr, first, bc1, bc2] read by the kernel in
     place of ``lr`` / ``first`` — the HIP-graph replay path (mivod.torch.graphs).
-    ``skip``: device int32 flag; nonzero => no update (fp16-wire overflow guard)."""
+    ``skip``: device int32 flag; nonzero => no update (fp16-wire overflow guard).
+    ``gclip`` (every step takes it): device fp32 clip coefficient (``clip_finalize``); the
+    step runs with gscale * gclip[0], one fp32 product."""
     if _on_gpu(g):
-        native().sgd_step(g, w, mom, model, float(lr), float(momentum), float(dampening),
-                          float(weight_decay), float(gscale), bool(nesterov), bool(first), dyn,
-                          skip)
+        args = (g, w, mom, model, float(lr), float(momentum), float(dampening),
+                float(weight_decay), float(gscale), bool(nesterov), bool(first), dyn, skip)
+        if gclip is None:
+            native().sgd_step(*args)
+        else:
+            native()._clip.sgd_step(*args, gclip)
         return
     if _skipped(skip):
         return
+    gscale = _clipped(gscale, gclip)
     d = g.float() * gscale + weight_decay * w
     if mom is not None:
         if first:
@@ -156,14 +248,19 @@ def sgd_step(g, w, mom, model, *, lr, momentum=0.0, dampening=0.0, weight_decay=
 
 
 def adam_step(g, w, m, v, model, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
-              gscale=1.0, step=1, adamw=False, keras_eps=False, dyn=None, skip=None):
+              gscale=1.0, step=1, adamw=False, keras_eps=False, dyn=None, skip=None, gclip=None):
     if _on_gpu(g):
-        native().adam_step(g, w, m, v, model, float(lr), float(beta1), float(beta2), float(eps),
-                           float(weight_decay), float(gscale), int(step), bool(adamw),
-                           bool(keras_eps), dyn, skip)
+        args = (g, w, m, v, model, float(lr), float(beta1), float(beta2), float(eps),
+                float(weight_decay), float(gscale), int(step), bool(adamw), bool(keras_eps), dyn,
+                skip)
+        if gclip is None:
+            native().adam_step(*args)
+        else:
+            native()._clip.adam_step(*args, gclip)
         return
     if _skipped(skip):
         return
+    gscale = _clipped(gscale, gclip)
     gr = g.float() * gscale
     if not adamw and weight_decay:
         gr = gr + weight_decay * w
@@ -183,13 +280,18 @@ def adam_step(g, w, m, v, model, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight
 
 
 def adadelta_step(g, w, sq, acc, model, *, lr=1.0, rho=0.9, eps=1e-6, weight_decay=0.0,
-                  gscale=1.0, dyn=None, skip=None):
+                  gscale=1.0, dyn=None, skip=None, gclip=None):
     if _on_gpu(g):
-        native().adadelta_step(g, w, sq, acc, model, float(lr), float(rho), float(eps),
-                               float(weight_decay), float(gscale), dyn, skip)
+        args = (g, w, sq, acc, model, float(lr), float(rho), float(eps), float(weight_decay),
+                float(gscale), dyn, skip)
+        if gclip is None:
+            native().adadelta_step(*args)
+        else:
+            native()._clip.adadelta_step(*args, gclip)
         return
     if _skipped(skip):
         return
+    gscale = _clipped(gscale, gclip)
     gr = g.float() * gscale + weight_decay * w
     sq.mul_(rho).addcmul_(gr, gr, value=1 - rho)
     delta = (acc + eps).sqrt() / (sq + eps).sqrt() * gr
@@ -200,7 +302,7 @@ def adadelta_step(g, w, sq, acc, model, *, lr=1.0, rho=0.9, eps=1e-6, weight_dec
 
 
 def rmsprop_step(g, w, sq, ga, buf, model, *, lr, alpha=0.99, eps=1e-8, weight_decay=0.0,
-                 momentum=0.0, centered=False, gscale=1.0, dyn=None, skip=None):
+                 momentum=0.0, centered=False, gscale=1.0, dyn=None, skip=None, gclip=None):
     """RMSprop with torch.optim.RMSprop's semantics (eps outside the root, lr outside the
     momentum buffer).  With gr = g * gscale + wd * w: sq = alpha sq + (1-alpha) gr^2;
     centered: ga = alpha ga + (1-alpha) gr and avg = sqrt(max(sq - ga^2, 0)) + eps, else
@@ -215,12 +317,16 @@ def rmsprop_step(g, w, sq, ga, buf, model, *, lr, alpha=0.99, eps=1e-8, weight_d
     if not centered:
         ga = None
     if _on_gpu(g):
-        native()._adaptive.rmsprop_step(g, w, sq, ga, buf, model, float(lr), float(alpha),
-                                        float(eps), float(weight_decay), float(momentum),
-                                        float(gscale), dyn, skip)
+        args = (g, w, sq, ga, buf, model, float(lr), float(alpha), float(eps),
+                float(weight_decay), float(momentum), float(gscale), dyn, skip)
+        if gclip is None:
+            native()._adaptive.rmsprop_step(*args)
+        else:
+            native()._clip.rmsprop_step(*args, gclip)
         return
     if _skipped(skip):
         return
+    gscale = _clipped(gscale, gclip)
     gr = g.float() * gscale + weight_decay * w
     sq.mul_(alpha).addcmul_(gr, gr, value=1 - alpha)
     if ga is not None:
@@ -238,16 +344,21 @@ def rmsprop_step(g, w, sq, ga, buf, model, *, lr, alpha=0.99, eps=1e-8, weight_d
 
 
 def adagrad_step(g, w, sum, model, *, lr, eps=1e-10, weight_decay=0.0, gscale=1.0, dyn=None,
-                 skip=None):
+                 skip=None, gclip=None):
     """Adagrad with torch.optim.Adagrad's semantics: gr = g * gscale + wd * w, sum += gr^2,
     w -= lr gr / (sqrt(sum) + eps).  ``lr`` is the decayed rate lr0 / (1 + (step-1) lr_decay)
     of this step, taken by the caller; ``dyn[0]`` replaces it."""
     if _on_gpu(g):
-        native()._adaptive.adagrad_step(g, w, sum, model, float(lr), float(eps),
-                                        float(weight_decay), float(gscale), dyn, skip)
+        args = (g, w, sum, model, float(lr), float(eps), float(weight_decay), float(gscale), dyn,
+                skip)
+        if gclip is None:
+            native()._adaptive.adagrad_step(*args)
+        else:
+            native()._clip.adagrad_step(*args, gclip)
         return
     if _skipped(skip):
         return
+    gscale = _clipped(gscale, gclip)
     gr = g.float() * gscale + weight_decay * w
     sum.addcmul_(gr, gr)
     w.sub_(lr * (gr / sum.sqrt().add_(eps)))
@@ -321,9 +432,10 @@ def _check_table(table: ChunkTable, numel: int) -> None:
 
 def lars_step(g, w, mom, model, table: ChunkTable, seg_flags: torch.Tensor, *, lr, momentum=0.9,
               weight_decay=0.0, eta=0.001, gscale=1.0, eps=0.0, first=False,
-              workspace: Optional[dict] = None, dyn=None, skip=None):
+              workspace: Optional[dict] = None, dyn=None, skip=None, gclip=None):
     """Segmented LARS (You et al. 2017): per segment trust = eta*|w|/(|g|+wd*|w|);
-    flagged segments (bit0) get trust 1 and no weight decay."""
+    flagged segments (bit0) get trust 1 and no weight decay.  With ``gclip`` the norm |g| is
+    that of the clipped gradient."""
     _check_table(table, g.numel())
     if _on_gpu(g):
         ws = workspace if workspace is not None else {}
@@ -334,13 +446,17 @@ def lars_step(g, w, mom, model, table: ChunkTable, seg_flags: torch.Tensor, *, l
         norms = ws.get("norms")
         if norms is None or norms.numel() < 2 * table.nseg:
             norms = ws["norms"] = torch.empty(2 * table.nseg, dtype=torch.float32, device=g.device)
-        native().lars_step(g, w, mom, model, table.begin, table.len, table.seg, table.seg_c0,
-                           table.seg_nc, seg_flags, partial, norms, float(lr), float(momentum),
-                           float(weight_decay), float(eta), float(gscale), float(eps), bool(first),
-                           dyn, skip)
+        args = (g, w, mom, model, table.begin, table.len, table.seg, table.seg_c0, table.seg_nc,
+                seg_flags, partial, norms, float(lr), float(momentum), float(weight_decay),
+                float(eta), float(gscale), float(eps), bool(first), dyn, skip)
+        if gclip is None:
+            native().lars_step(*args)
+        else:
+            native()._clip.lars_step(*args, gclip)
         return
     if _skipped(skip):
         return
+    gscale = _clipped(gscale, gclip)
     flags = seg_flags.tolist()
     for i, (off, n) in enumerate(zip(table.seg_offsets, table.seg_sizes)):
         sl = slice(off, off + n)
@@ -363,7 +479,7 @@ def lars_step(g, w, mom, model, table: ChunkTable, seg_flags: torch.Tensor, *, l
 
 def lamb_step(g, w, m, v, model, table: ChunkTable, seg_flags: torch.Tensor, *, lr, beta1=0.9,
               beta2=0.999, eps=1e-6, weight_decay=0.0, gscale=1.0, step=1,
-              workspace: Optional[dict] = None, dyn=None, skip=None):
+              workspace: Optional[dict] = None, dyn=None, skip=None, gclip=None):
     """Segmented LAMB (You et al. 2019).  Per segment, with gr = g * gscale:
     m = b1 m + (1-b1) gr, v = b2 v + (1-b2) gr^2, u = (m/bc1) / (sqrt(v/bc2) + eps) + wd w,
     trust = |w| / |u| when both norms are positive (else 1), w -= lr trust u.  Flagged
@@ -380,13 +496,17 @@ def lamb_step(g, w, m, v, model, table: ChunkTable, seg_flags: torch.Tensor, *, 
         norms = ws.get("norms")
         if norms is None or norms.numel() < 2 * table.nseg:
             norms = ws["norms"] = torch.empty(2 * table.nseg, dtype=torch.float32, device=g.device)
-        native()._lamb.lamb_step(g, w, m, v, model, table.begin, table.len, table.seg,
-                                 table.seg_c0, table.seg_nc, seg_flags, partial, norms, float(lr),
-                                 float(beta1), float(beta2), float(eps), float(weight_decay),
-                                 float(gscale), int(step), dyn, skip)
+        args = (g, w, m, v, model, table.begin, table.len, table.seg, table.seg_c0, table.seg_nc,
+                seg_flags, partial, norms, float(lr), float(beta1), float(beta2), float(eps),
+                float(weight_decay), float(gscale), int(step), dyn, skip)
+        if gclip is None:
+            native()._lamb.lamb_step(*args)
+        else:
+            native()._clip.lamb_step(*args, gclip)
         return
     if _skipped(skip):
         return
+    gscale = _clipped(gscale, gclip)
     bc1 = 1 - beta1 ** step
     bc2 = 1 - beta2 ** step
     flags = seg_flags.tolist()

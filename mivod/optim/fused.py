@@ -18,6 +18,7 @@ and LARS (large-batch ResNet), per BASELINE.json north star.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional
 
 import torch
@@ -29,6 +30,17 @@ ALIGN = 64  # elements; keeps every slot 16-byte aligned for bf16/fp16/fp32
 
 def _align(n: int) -> int:
     return (n + ALIGN - 1) // ALIGN * ALIGN
+
+
+def check_max_grad_norm(v):
+    """``max_grad_norm`` as a float, or None when clipping is off; a value that is not a
+    positive finite number raises."""
+    if v is None:
+        return None
+    f = float(v)
+    if not (math.isfinite(f) and f > 0.0):
+        raise ValueError(f"max_grad_norm must be a positive finite number or None, not {v!r}")
+    return f
 
 
 class Arena:
@@ -108,17 +120,34 @@ class Arena:
 
 
 class FusedOptimizer(torch.optim.Optimizer):
-    """Base class: arena management, standalone ``step()``, state-dict views."""
+    """Base class: arena management, standalone ``step()``, state-dict views.
+
+    ``max_grad_norm`` (every ``Fused*`` constructor takes it; default None = off) clips the
+    global L2 norm of the gradient, over all param groups and arenas, to that value before
+    the update, as ``torch.nn.utils.clip_grad_norm_`` does: the gradient is scaled by
+    min(1, max_grad_norm / (norm + 1e-6)).  The norm, the coefficient and the scaling stay
+    on the device (csrc/kernels/mv_clip.hip; the step kernels multiply their gradient scale
+    by the coefficient), so there is no host synchronisation, and under
+    ``mivod.torch.DistributedOptimizer`` the norm is that of the reduced (averaged) gradient
+    with no extra collective.  It is a plain attribute, not part of ``param_groups`` or
+    ``state_dict()``, and may be changed or set to None between eager steps; a HIP graph
+    keeps the value it was captured with.  ``grad_norm()`` reads the last measured norm."""
 
     _state_names: List[str] = []
 
-    def __init__(self, params, defaults, grad_dtype: Optional[torch.dtype] = None):
+    def __init__(self, params, defaults, grad_dtype: Optional[torch.dtype] = None,
+                 max_grad_norm: Optional[float] = None):
         super().__init__(params, defaults)
         self._mv_arenas: Optional[List[Arena]] = None
         self._mv_grad_dtype = grad_dtype
         self._mv_external_grads = False   # True when DistributedOptimizer packs grads
         self._mv_graph = False            # True while a HIP graph captures the step
         self._mv_skip = None              # device int32 skip flag (overflow guard)
+        self._mv_clip = None              # device fp32 clip coefficient the step kernels read
+        self._mv_clip_block = None        # device fp32 [coefficient, norm] of the last step
+        self._mv_clip_ws = None           # fp32 sum-of-squares partials, one per 4096 elements
+        check_max_grad_norm(max_grad_norm)
+        self.max_grad_norm = max_grad_norm
 
     # ---- layout ----------------------------------------------------------
     def _mv_build(self, grad_dtype_for=None) -> List[Arena]:
@@ -184,7 +213,50 @@ class FusedOptimizer(torch.optim.Optimizer):
         st = {n: f[lo:hi] for n, f in a.state.items()}
         return a.grad[lo:hi], a.master[lo:hi], st, model
 
+    # ---- global gradient-norm clipping ------------------------------------
+    def _mv_clip_buffers(self, device, nchunks: int):
+        """The device block [coefficient, norm] and a partial workspace of at least
+        ``nchunks`` entries (kept: a captured HIP graph holds their addresses)."""
+        blk = self._mv_clip_block
+        if blk is None or blk.device != device:
+            blk = self._mv_clip_block = torch.tensor([1.0, 0.0], dtype=torch.float32,
+                                                     device=device)
+        ws = self._mv_clip_ws
+        if ws is None or ws.device != device or ws.numel() < nchunks:
+            ws = self._mv_clip_ws = torch.empty(max(nchunks, 1), dtype=torch.float32,
+                                                device=device)
+        return blk, ws
+
+    def grad_norm(self) -> torch.Tensor:
+        """The global L2 norm of the last clipped step's gradient before clipping (under
+        DistributedOptimizer: of the averaged gradient), a 0-dim device tensor.  No host
+        synchronisation happens here; ``.item()`` is the caller's."""
+        if self._mv_clip_block is None:
+            raise RuntimeError("grad_norm(): no step has run with max_grad_norm set")
+        return self._mv_clip_block[1].clone()
+
     # ---- standalone step (no DistributedOptimizer) -------------------------
+    def _mv_pack_local(self, a: Arena):
+        """p.grad of every parameter of ``a`` -> its slot of the flat gradient arena."""
+        grads, offs = [], []
+        for i, p in enumerate(a.params):
+            if p.grad is None:
+                lo = a.offsets[i]
+                a.grad[lo:lo + p.numel()].zero_()
+                continue
+            g = p.grad
+            if g.stride() != p.stride():
+                g = torch.empty_like(p).copy_(g)
+            grads.append(g)
+            offs.append(a.offsets[i])
+        by_dt: Dict[torch.dtype, tuple] = {}
+        for g, o in zip(grads, offs):
+            by_dt.setdefault(g.dtype, ([], []))
+            by_dt[g.dtype][0].append(g)
+            by_dt[g.dtype][1].append(o)
+        for gl, ol in by_dt.values():
+            K.pack(gl, a.grad, ol)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -193,27 +265,31 @@ class FusedOptimizer(torch.optim.Optimizer):
                 loss = closure()
         arenas = self._mv_build()
         self._mv_begin_step()
-        for a in arenas:
+        max_norm = check_max_grad_norm(self.max_grad_norm)
+        if max_norm is None:
+            for a in arenas:
+                if not self._mv_external_grads:
+                    self._mv_pack_local(a)
+                self._mv_apply(a, 0, len(a.params), 1.0)
+        elif arenas:
+            # every arena packed and measured before the first update: the coefficient is
+            # global.  The alignment gaps of an arena are zeros, so its whole range is summed.
             if not self._mv_external_grads:
-                grads, offs = [], []
-                for i, p in enumerate(a.params):
-                    if p.grad is None:
-                        lo = a.offsets[i]
-                        a.grad[lo:lo + p.numel()].zero_()
-                        continue
-                    g = p.grad
-                    if g.stride() != p.stride():
-                        g = torch.empty_like(p).copy_(g)
-                    grads.append(g)
-                    offs.append(a.offsets[i])
-                by_dt: Dict[torch.dtype, tuple] = {}
-                for g, o in zip(grads, offs):
-                    by_dt.setdefault(g.dtype, ([], []))
-                    by_dt[g.dtype][0].append(g)
-                    by_dt[g.dtype][1].append(o)
-                for gl, ol in by_dt.values():
-                    K.pack(gl, a.grad, ol)
-            self._mv_apply(a, 0, len(a.params), 1.0)
+                for a in arenas:
+                    self._mv_pack_local(a)
+            counts = [K.sumsq_chunks(a.numel) for a in arenas]
+            blk, ws = self._mv_clip_buffers(arenas[0].device, sum(counts))
+            o = 0
+            for a, c in zip(arenas, counts):
+                K.grad_sumsq(a.grad, ws[o:o + c])
+                o += c
+            K.clip_finalize(ws, o, blk, gscale=1.0, max_norm=max_norm)
+            self._mv_clip = blk[0:1]
+            try:
+                for a in arenas:
+                    self._mv_apply(a, 0, len(a.params), 1.0)
+            finally:
+                self._mv_clip = None
         self._mv_end_step()
         return loss
 
@@ -258,12 +334,13 @@ class FusedSGD(FusedOptimizer):
     semantics, momentum buffer seeded with the first gradient)."""
 
     def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,
-                 nesterov=False, grad_dtype=None):
+                 nesterov=False, grad_dtype=None, max_grad_norm=None):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         self._state_names = ["momentum_buffer"] if momentum != 0 else []
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening,
-                                      weight_decay=weight_decay, nesterov=nesterov), grad_dtype)
+                                      weight_decay=weight_decay, nesterov=nesterov), grad_dtype,
+                         max_grad_norm)
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
         g, w, st, model = self._mv_slices(a, i0, i1)
@@ -271,7 +348,7 @@ class FusedSGD(FusedOptimizer):
         K.sgd_step(g, w, st.get("momentum_buffer"), model, lr=hp["lr"], momentum=hp["momentum"],
                    dampening=hp["dampening"], weight_decay=hp["weight_decay"], gscale=gscale,
                    nesterov=hp["nesterov"], first=(a.step == 1), dyn=self._mv_dyn(a),
-                   skip=self._mv_skip)
+                   skip=self._mv_skip, gclip=self._mv_clip)
 
 
 class FusedAdam(FusedOptimizer):
@@ -281,9 +358,10 @@ class FusedAdam(FusedOptimizer):
     _state_names = ["exp_avg", "exp_avg_sq"]
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 adamw=False, keras_eps=False, grad_dtype=None):
+                 adamw=False, keras_eps=False, grad_dtype=None, max_grad_norm=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      adamw=adamw, keras_eps=keras_eps), grad_dtype)
+                                      adamw=adamw, keras_eps=keras_eps), grad_dtype,
+                         max_grad_norm)
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
         g, w, st, model = self._mv_slices(a, i0, i1)
@@ -292,13 +370,14 @@ class FusedAdam(FusedOptimizer):
         K.adam_step(g, w, st["exp_avg"], st["exp_avg_sq"], model, lr=hp["lr"], beta1=b1, beta2=b2,
                     eps=hp["eps"], weight_decay=hp["weight_decay"], gscale=gscale, step=a.step,
                     adamw=hp["adamw"], keras_eps=hp["keras_eps"], dyn=self._mv_dyn(a),
-                    skip=self._mv_skip)
+                    skip=self._mv_skip, gclip=self._mv_clip)
 
 
 class FusedAdamW(FusedAdam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 grad_dtype=None):
-        super().__init__(params, lr, betas, eps, weight_decay, adamw=True, grad_dtype=grad_dtype)
+                 grad_dtype=None, max_grad_norm=None):
+        super().__init__(params, lr, betas, eps, weight_decay, adamw=True, grad_dtype=grad_dtype,
+                         max_grad_norm=max_grad_norm)
 
 
 class FusedAdadelta(FusedOptimizer):
@@ -306,16 +385,17 @@ class FusedAdadelta(FusedOptimizer):
 
     _state_names = ["square_avg", "acc_delta"]
 
-    def __init__(self, params, lr=1.0, rho=0.9, eps=1e-6, weight_decay=0.0, grad_dtype=None):
+    def __init__(self, params, lr=1.0, rho=0.9, eps=1e-6, weight_decay=0.0, grad_dtype=None,
+                 max_grad_norm=None):
         super().__init__(params, dict(lr=lr, rho=rho, eps=eps, weight_decay=weight_decay),
-                         grad_dtype)
+                         grad_dtype, max_grad_norm)
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
         g, w, st, model = self._mv_slices(a, i0, i1)
         hp = a.group
         K.adadelta_step(g, w, st["square_avg"], st["acc_delta"], model, lr=hp["lr"], rho=hp["rho"],
                         eps=hp["eps"], weight_decay=hp["weight_decay"], gscale=gscale,
-                        dyn=self._mv_dyn(a), skip=self._mv_skip)
+                        dyn=self._mv_dyn(a), skip=self._mv_skip, gclip=self._mv_clip)
 
 
 class FusedLARS(FusedOptimizer):
@@ -326,9 +406,9 @@ class FusedLARS(FusedOptimizer):
     _state_names = ["momentum_buffer"]
 
     def __init__(self, params, lr=0.1, momentum=0.9, weight_decay=1e-4, eta=0.001, eps=0.0,
-                 exclude_1d=True, grad_dtype=None):
+                 exclude_1d=True, grad_dtype=None, max_grad_norm=None):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, eta=eta,
-                                      eps=eps, exclude_1d=exclude_1d), grad_dtype)
+                                      eps=eps, exclude_1d=exclude_1d), grad_dtype, max_grad_norm)
         self._mv_flags: Dict[tuple, torch.Tensor] = {}
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
@@ -342,7 +422,7 @@ class FusedLARS(FusedOptimizer):
         K.lars_step(g, w, st["momentum_buffer"], model, a.table(i0, i1), flags, lr=hp["lr"],
                     momentum=hp["momentum"], weight_decay=hp["weight_decay"], eta=hp["eta"],
                     gscale=gscale, eps=hp["eps"], first=(a.step == 1), workspace=a.workspace,
-                    dyn=self._mv_dyn(a), skip=self._mv_skip)
+                    dyn=self._mv_dyn(a), skip=self._mv_skip, gclip=self._mv_clip)
 
 
 class FusedLAMB(FusedOptimizer):
@@ -352,16 +432,20 @@ class FusedLAMB(FusedOptimizer):
     weight decay and trust 1 when ``exclude_1d=True``; with ``exclude_1d=False`` every
     tensor is adapted and decayed.
 
-    Not provided: global gradient-norm clipping (``max_grad_norm``: it needs every bucket
-    reduced before the first update, which the overlapped per-bucket step does not wait
-    for), trust-ratio clamping, ``grad_averaging=False`` and an ``always_adapt`` switch."""
+    ``max_grad_norm`` clips the global gradient norm before the moments are updated (the
+    BERT pre-training recipe; see ``FusedOptimizer``): every bucket is reduced and measured
+    before the first update, so under DistributedOptimizer the updates are not overlapped
+    with backward while it is set.
+
+    Not provided: trust-ratio clamping, ``grad_averaging=False`` and an ``always_adapt``
+    switch."""
 
     _state_names = ["exp_avg", "exp_avg_sq"]
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01,
-                 exclude_1d=True, grad_dtype=None):
+                 exclude_1d=True, grad_dtype=None, max_grad_norm=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      exclude_1d=exclude_1d), grad_dtype)
+                                      exclude_1d=exclude_1d), grad_dtype, max_grad_norm)
         self._mv_flags: Dict[tuple, torch.Tensor] = {}
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
@@ -376,7 +460,8 @@ class FusedLAMB(FusedOptimizer):
         K.lamb_step(g, w, st["exp_avg"], st["exp_avg_sq"], model, a.table(i0, i1), flags,
                     lr=hp["lr"], beta1=b1, beta2=b2, eps=hp["eps"],
                     weight_decay=hp["weight_decay"], gscale=gscale, step=a.step,
-                    workspace=a.workspace, dyn=self._mv_dyn(a), skip=self._mv_skip)
+                    workspace=a.workspace, dyn=self._mv_dyn(a), skip=self._mv_skip,
+                    gclip=self._mv_clip)
 
 
 class FusedRMSprop(FusedOptimizer):
@@ -389,13 +474,14 @@ class FusedRMSprop(FusedOptimizer):
     non-zero values."""
 
     def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0,
-                 centered=False, grad_dtype=None):
+                 centered=False, grad_dtype=None, max_grad_norm=None):
         if lr < 0 or eps < 0 or alpha < 0 or momentum < 0 or weight_decay < 0:
             raise ValueError("FusedRMSprop: lr, alpha, eps, momentum and weight_decay must be >= 0")
         self._state_names = (["square_avg"] + (["momentum_buffer"] if momentum != 0 else [])
                              + (["grad_avg"] if centered else []))
         super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay,
-                                      momentum=momentum, centered=bool(centered)), grad_dtype)
+                                      momentum=momentum, centered=bool(centered)), grad_dtype,
+                         max_grad_norm)
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
         g, w, st, model = self._mv_slices(a, i0, i1)
@@ -404,7 +490,7 @@ class FusedRMSprop(FusedOptimizer):
                        lr=hp["lr"], alpha=hp["alpha"], eps=hp["eps"],
                        weight_decay=hp["weight_decay"], momentum=hp["momentum"],
                        centered=hp["centered"], gscale=gscale, dyn=self._mv_dyn(a),
-                       skip=self._mv_skip)
+                       skip=self._mv_skip, gclip=self._mv_clip)
 
 
 class FusedAdagrad(FusedOptimizer):
@@ -416,13 +502,13 @@ class FusedAdagrad(FusedOptimizer):
     _state_names = ["sum"]
 
     def __init__(self, params, lr=1e-2, lr_decay=0, weight_decay=0, initial_accumulator_value=0,
-                 eps=1e-10, grad_dtype=None):
+                 eps=1e-10, grad_dtype=None, max_grad_norm=None):
         if lr < 0 or lr_decay < 0 or weight_decay < 0 or initial_accumulator_value < 0 or eps < 0:
             raise ValueError("FusedAdagrad: lr, lr_decay, weight_decay, "
                              "initial_accumulator_value and eps must be >= 0")
         super().__init__(params, dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay,
                                       initial_accumulator_value=initial_accumulator_value),
-                         grad_dtype)
+                         grad_dtype, max_grad_norm)
 
     def _mv_build(self, grad_dtype_for=None):
         if self._mv_arenas is None:
@@ -441,4 +527,4 @@ class FusedAdagrad(FusedOptimizer):
         clr = hp["lr"] / (1.0 + (a.step - 1) * hp["lr_decay"])
         K.adagrad_step(g, w, st["sum"], model, lr=clr, eps=hp["eps"],
                        weight_decay=hp["weight_decay"], gscale=gscale, dyn=self._mv_dyn(a),
-                       skip=self._mv_skip)
+                       skip=self._mv_skip, gclip=self._mv_clip)

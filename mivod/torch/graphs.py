@@ -32,6 +32,11 @@ What makes a replay equal to an eager step:
 
 The bucket schedule is frozen by the capture (autotuning is switched off) and
 every replay is a full step, so ``backward_passes_per_step`` must be 1.
+A fused optimizer's ``max_grad_norm`` is captured like the rest of the step (the
+norm pass, the finalize and the clipped updates are kernels on device operands),
+but its VALUE is a launch argument of the finalize kernel: the graph keeps the
+value it was captured with, and changing the attribute afterwards affects eager
+steps only.
 
 Measured (1x MI355X, ROCm 7): ResNet-50 replays are correct but not faster than
 eager at bs 128-1024 — the step is GPU-bound and ROCm replays the two-stream

@@ -42,6 +42,19 @@ MI355X design (not a translation of horovod's per-tensor async ops):
   scales the wire by s (halved after an overflow, doubled back after
   ``GUARD_GROWTH_STEPS`` (200) clean steps, capped at 1) and folds 1/s into the
   update.
+* **Global gradient-norm clipping** (``max_grad_norm`` of the wrapped ``Fused*``
+  optimizer): horovod's ``synchronize()`` / ``clip_grad_norm_`` /
+  ``skip_synchronize()`` pattern needs ``p.grad`` after the reduction, which the
+  fused path has already consumed.  Instead each REDUCED bucket's sum of squares
+  is taken on the comm stream (``grad_sumsq``: deterministic per-chunk partials
+  into a fixed slice of one workspace; with the guard on the same launch sets the
+  overflow flag, so it replaces the scan), every fused update is deferred to
+  ``synchronize()``, where one ``clip_finalize`` launch turns the partials into
+  the coefficient min(1, max_norm / (norm + 1e-6)) on the device and the updates
+  of all buckets follow in plan order, reading it.  Every rank holds the same
+  reduced bits, so every rank clips identically with no extra collective and no
+  host wait; the price is that the updates no longer overlap backward (with the
+  guard in "step" mode they already do not).
 * **Timeline**: with ``HOROVOD_TIMELINE`` set, every bucket's pack / collective
   / fused step is recorded with GPU timestamps (``utils.timeline.PhaseRecorder``).
 """
@@ -57,7 +70,7 @@ import torch
 from ..common import basics
 from ..ops import kernels as K
 from ..ops.compression import Compression
-from ..optim.fused import Arena, FusedOptimizer, _align
+from ..optim.fused import Arena, FusedOptimizer, _align, check_max_grad_norm
 from ..parallel import collectives as C
 from ..parallel.order import ORDER
 from ..utils import markers as MK
@@ -292,6 +305,13 @@ class _DistributedOptimizerMixin:
         self._mvd_guard_mode = os.environ.get("MIVOD_GUARD_MODE", "step")
         if self._mvd_guard_mode not in ("bucket", "step"):
             raise ValueError("MIVOD_GUARD_MODE must be 'bucket' or 'step'")
+        # global gradient-norm clipping: a fused optimizer's max_grad_norm (read again at
+        # every step's start, so it may change between eager steps)
+        self._mvd_clip_norm = None        # this step's max_grad_norm (None: off)
+        self._mvd_clip_slices = None      # ({bucket index: (offset, count)}, total) of the
+        #                                   partial workspace, laid out from the bucket plan
+        if self._mvd_fused:
+            self._mvd_clip_check(check_max_grad_norm(self.max_grad_norm))
         self._mvd_flag = None             # device int32 non-finite flags of the step
         self._mvd_flag_host = None        # pinned copy + event of the previous step's flags
         self._mvd_flag_ev = None
@@ -321,7 +341,8 @@ class _DistributedOptimizerMixin:
         h = hashlib.blake2b(digest_size=8)
         h.update(repr((C.op_name(self._mvd_op), self._mvd_compression.__name__,
                        self._mvd_bpps, self._mvd_guard, self._mvd_gs,
-                       self._mvd_guard_mode if self._mvd_guard else "")).encode())
+                       self._mvd_guard_mode if self._mvd_guard else "",
+                       self.max_grad_norm if self._mvd_fused else None)).encode())
         for b in self._mvd_buckets:
             h.update(repr((str(b.arena.grad.dtype), b.hi - b.lo,
                            [(self._mvd_names[id(p)], tuple(p.shape)) for p in b.params])).encode())
@@ -331,7 +352,58 @@ class _DistributedOptimizerMixin:
             raise ValueError(
                 "mivod DistributedOptimizer: the static gradient schedule differs across ranks "
                 f"(plan hashes {sorted(set(every.tolist()))}); every rank must wrap the same "
-                "model with the same parameter order, dtypes, op, compression and bucket settings")
+                "model with the same parameter order, dtypes, op, compression, max_grad_norm and "
+                "bucket settings")
+
+    # ------------------------------------------------- gradient-norm clipping
+    def _mvd_clip_check(self, max_norm):
+        if max_norm is not None and self._mvd_guard and self._mvd_guard_mode == "bucket":
+            raise ValueError("max_grad_norm cannot be combined with MIVOD_GUARD_MODE=bucket: a "
+                             "step of which only some buckets are applied has no global norm "
+                             "to clip by")
+        return max_norm
+
+    def _mvd_clip_layout(self):
+        """Every bucket's fixed slice of the partial workspace, in plan order."""
+        if self._mvd_clip_slices is None:
+            sl, o = {}, 0
+            for b in self._mvd_buckets:
+                c = K.sumsq_chunks(b.hi - b.lo)
+                sl[b.index] = (o, c)
+                o += c
+            self._mvd_clip_slices = (sl, o)
+        return self._mvd_clip_slices
+
+    def _mvd_gscale(self) -> float:
+        """The gradient scale of the fused updates: the wire scale undone, the average."""
+        gscale = 1.0 / self._mvd_gs
+        if self._mvd_op == C.Average:
+            gscale *= self._mvd_predivide / self._mvd_size
+        return gscale
+
+    def _mvd_clip_finish(self):
+        """synchronize() with max_grad_norm set, after the last bucket is reduced and
+        measured: the coefficient from the partials of every bucket, then every bucket's
+        fused update in plan order (through ``_mvd_guard_finish`` with the guard on)."""
+        _, total = self._mvd_clip_layout()
+        blk, ws = self._mv_clip_buffers(self._mvd_buckets[0].arena.grad.device, total)
+        cuda = ws.is_cuda and self._mvd_stream is not None and not self._mvd_inline
+        with (torch.cuda.stream(self._mvd_stream) if cuda else contextlib.nullcontext()):
+            K.clip_finalize(ws, total, blk, gscale=self._mvd_gscale(),
+                            max_norm=self._mvd_clip_norm)
+            self._mv_clip = blk[0:1]
+            try:
+                if self._mvd_guard:
+                    self._mvd_guard_finish()
+                else:
+                    for b in self._mvd_buckets:
+                        self._mvd_apply_bucket(b, cuda)
+                    if cuda:
+                        ev2 = torch.cuda.Event()
+                        ev2.record()
+                        self._mvd_done_event = ev2
+            finally:
+                self._mv_clip = None
 
     # --------------------------------------------------------------- hot path
     def _mvd_hook(self, p: torch.Tensor):
@@ -463,6 +535,10 @@ class _DistributedOptimizerMixin:
                 self._mvd_guard_begin(a.grad.device)
             if self._mvd_fused:
                 self._mv_begin_step()
+                self._mvd_clip_norm = self._mvd_clip_check(
+                    check_max_grad_norm(self.max_grad_norm))
+                if self._mvd_clip_norm is not None:
+                    self._mv_clip_buffers(a.grad.device, self._mvd_clip_layout()[1])
         size = self._mvd_size
         prescale = 1.0 / self._mvd_predivide if self._mvd_op == C.Average else 1.0
         prescale *= self._mvd_gs
@@ -570,13 +646,22 @@ class _DistributedOptimizerMixin:
                                 "NCCL_ALLREDUCE" if cuda else "RING_ALLREDUCE"))
                         rec.add(b.name, phase, t0, rec.event() if cuda else rec.host())
         with (torch.cuda.stream(self._mvd_stream) if cuda else contextlib.nullcontext()):
-            if self._mvd_guard and not scan_in_pack:
+            clip = self._mvd_clip_norm is not None
+            if clip:
+                # the REDUCED bucket's sum of squares into its slice of the workspace; the
+                # guard's scan (when it did not ride in the pack) is the same launch
+                o, c = self._mvd_clip_layout()[0][b.index]
+                K.grad_sumsq(flat, self._mv_clip_ws[o:o + c],
+                             self._mvd_bucket_flag(b) if self._mvd_guard and not scan_in_pack
+                             else None)
+            elif self._mvd_guard and not scan_in_pack:
                 # overflow guard: scan the REDUCED bucket (a non-finite contribution
                 # of any rank, or an fp16 overflow in the reduction, is non-finite
                 # here, identically on every rank — no extra collective)
                 K.nonfinite_scan(flat, self._mvd_bucket_flag(b))
             if self._mvd_fused:
-                if not self._mvd_guard or self._mvd_guard_mode == "bucket":
+                # with clipping on, every update waits for the coefficient (synchronize())
+                if not clip and (not self._mvd_guard or self._mvd_guard_mode == "bucket"):
                     self._mvd_apply_bucket(b, cuda)
             else:
                 post = self._mvd_predivide if (self._mvd_op == C.Average and size > 1) else 1.0
@@ -622,9 +707,7 @@ class _DistributedOptimizerMixin:
     def _mvd_apply_bucket(self, b: _Bucket, cuda: bool):
         """The fused optimizer step of one reduced bucket (current stream)."""
         rec = self._mvd_rec
-        gscale = 1.0 / self._mvd_gs
-        if self._mvd_op == C.Average:
-            gscale *= self._mvd_predivide / self._mvd_size
+        gscale = self._mvd_gscale()
         t0 = (rec.event() if cuda else rec.host()) if rec is not None else None
         self._mv_skip = self._mvd_bucket_flag(b) if self._mvd_guard else None
         with MK.range(f"mivod.step.{b.name}"):
@@ -692,7 +775,9 @@ class _DistributedOptimizerMixin:
                 if not b.launched:
                     b.pending = 0
             self._mvd_launch_ready()
-            if self._mvd_guard and self._mvd_in_step:
+            if self._mvd_in_step and self._mvd_clip_norm is not None:
+                self._mvd_clip_finish()
+            elif self._mvd_guard and self._mvd_in_step:
                 self._mvd_guard_finish()
             if self._mvd_stream is not None and torch.cuda.is_available() and \
                     not self._mvd_inline:
@@ -705,6 +790,7 @@ class _DistributedOptimizerMixin:
             self._mvd_counts.clear()
             self._mvd_next = 0
             self._mvd_in_step = False
+            self._mvd_clip_norm = None
             self._mvd_synchronized = True
             self._mvd_steps += 1
             if self._mvd_autotune is not None and not self._mvd_autotune.done:
@@ -717,6 +803,7 @@ class _DistributedOptimizerMixin:
                                          int(bucket_mb * 2 ** 20), self._mvd_position,
                                          self._mvd_last_bytes)
         self._mvd_where = {}
+        self._mvd_clip_slices = None      # the partial workspace follows the bucket plan
         self.__dict__.pop("_mvd_gap_cache", None)
         for b in self._mvd_buckets:
             for k, p in enumerate(b.params):
@@ -789,6 +876,9 @@ def DistributedOptimizer(optimizer, named_parameters=None, compression=None,
     ``compression`` defaults to ``MIVOD_COMPRESSION`` (``none``).  With an fp16
     wire the overflow guard is on unless ``overflow_guard=False``;
     ``grad_scale="dynamic"`` (or a float) scales the wire (see module doc).
+    A ``mivod.optim.Fused*`` optimizer's ``max_grad_norm`` clips the global norm of
+    the averaged gradient (see module doc); it must agree across ranks and cannot be
+    combined with ``MIVOD_GUARD_MODE=bucket``.
 
     Returns an instance of a dynamically created subclass of the optimizer's
     class (same class name, so ``isinstance`` and pickled configs keep working),
