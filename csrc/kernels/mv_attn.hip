@@ -546,7 +546,10 @@ __global__ __launch_bounds__(256) void bwd_kernel(AttnParams p, const __bf16* __
       *reinterpret_cast<bf16x8*>(&dOs[row][d0 + 8]) = o1;
       if (t < QB) {
         const int qq = qb0 + t;
-        lse_s[t] = qq < p.s ? p.lse[(int64_t)bh * p.s + qq] : INFINITY;
+        // a query whose keys are all masked to -inf has lse = -inf (out = 0): staged as
+        // +inf like a padding query, so its P is 0 (kbias - lse would be -inf + inf = NaN)
+        const float lv = qq < p.s ? p.lse[(int64_t)bh * p.s + qq] : INFINITY;
+        lse_s[t] = lv == -INFINITY ? INFINITY : lv;
         del_s[t] = qq < p.s ? delta[(int64_t)bh * p.s + qq] : 0.f;
       }
     }
@@ -712,6 +715,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void b
       y1 = ld_b128(Ob + (int64_t)row * otok + d0 + 8);
     }
     if (t < SQ && t < p.s) lse_v = p.lse[(int64_t)bh * p.s + t];
+    // a query whose keys are all masked to -inf has lse = -inf (out = 0): staged as +inf
+    // like a padding query, so its P is 0 (kbias - lse would be -inf + inf = NaN)
+    if (lse_v == -INFINITY) lse_v = INFINITY;
     *reinterpret_cast<bf16x8*>(&Ks[ks_off(row, d0)]) = ka;
     *reinterpret_cast<bf16x8*>(&Ks[ks_off(row, d0 + 8)]) = kb2;
     *reinterpret_cast<bf16x8*>(&Qs[row][d0]) = q0v;

@@ -8,6 +8,20 @@
   forward; FlashAttention-2-style backward with deterministic dQ partials).
 * anything else -> ``attention_math`` (batched GEMMs + fp32 softmax), which is
   also the numerics reference for the kernels.
+
+The mask contract
+-----------------
+``mask_bias`` is an additive bias per (batch row, key), in natural-log units like the scores
+(the kernels work in the log2 domain and scale it themselves), of any finite value, ``-inf``
+or ``finfo(float32).min`` (whose product with log2(e) overflows to ``-inf``).  A key at
+``-inf`` has probability exactly 0 and gets zero dK / dV rows.  A batch row whose keys are ALL
+at ``-inf`` (a fully padded sequence) has no softmax: the kernels give it ``out = 0`` and
+``lse = -inf``, and its backward contributes exactly zero gradients (the row's lse is staged
+as ``+inf``, so every recomputed probability is 0).  ``attention_math`` divides 0 by 0 there
+and yields NaN for such a row; only the kernels define it.  Other finite values
+below about -4e37 are not a supported way to say "masked" (the s <= 128 forward multiplies the
+mask by 8 ahead of the common score scale and overflows earlier than the other kernels): use ``-inf``, ``finfo.min``
+or a moderate value like -10000.
 """
 from __future__ import annotations
 
@@ -22,6 +36,9 @@ from . import kernels as K
 
 def attention_math(qkv: torch.Tensor, mask_bias=None, p_drop: float = 0.0,
                    keep_mask=None) -> torch.Tensor:
+    """The fallback for devices and dtypes the kernels do not cover.  A row whose keys are all
+    masked with ``-inf`` comes out NaN here (softmax of an empty set), where the kernels give
+    0: see the mask contract above."""
     b, s, _, h, d = qkv.shape
     q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)          # [b, h, s, d]
     scores = torch.matmul(q, k.transpose(-1, -2)).float() * (1.0 / math.sqrt(d))
