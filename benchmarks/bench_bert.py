@@ -5,6 +5,8 @@ with fp16 gradient compression + Adasum through mivod.torch.DistributedOptimizer
     python benchmarks/bench_bert.py --steps 20 --warmup 5
     python benchmarks/bench_bert.py --gpus 8          # spawns its own 8 ranks
     python benchmarks/bench_bert.py --max-grad-norm 1.0   # with global gradient-norm clipping
+    python benchmarks/bench_bert.py --backward-passes 4 --accumulation-dtype fp32
+                                                          # 4 micro-batches per step, summed in fp32
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
         benchmarks/bench_bert.py --gpus 8
 Prints one JSON line (sequences/sec for the whole job) with a ``comm`` record.
@@ -61,6 +63,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--max-grad-norm", type=float, default=None,
                     help="clip the global gradient norm (FusedAdam's max_grad_norm); default off")
+    ap.add_argument("--backward-passes", type=int, default=1,
+                    help="micro-batches of --batch sequences per optimizer step "
+                         "(backward_passes_per_step); default 1")
+    ap.add_argument("--accumulation-dtype", default="none", choices=["none", "fp32"],
+                    help="none: the passes accumulate in p.grad (bf16); fp32: in the fp32 arena")
     args = ap.parse_args()
     if args.gpus > 1 and not any(k in os.environ for k in ("WORLD_SIZE", "HOROVOD_RANK")):
         sys.path.insert(0, ROOT)
@@ -92,7 +99,12 @@ def main():
                     max_grad_norm=args.max_grad_norm)
     op = hvd.Adasum if args.op == "adasum" else hvd.Average
     opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(),
-                                   compression=hvd.Compression.by_name(args.compression), op=op)
+                                   compression=hvd.Compression.by_name(args.compression), op=op,
+                                   backward_passes_per_step=args.backward_passes,
+                                   accumulation_dtype=(torch.float32
+                                                       if args.accumulation_dtype == "fp32"
+                                                       else None))
+    passes = args.backward_passes
     hvd.broadcast_parameters(model.state_dict(), 0)
     hvd.broadcast_optimizer_state(opt, 0)
     g = torch.Generator(device=dev)
@@ -103,8 +115,9 @@ def main():
     timing = []
 
     def step(timed=False):
-        loss = model(*batch)
-        loss.backward()
+        for _ in range(passes):              # horovod semantics: the passes are summed
+            loss = model(*batch)
+            (loss if passes == 1 else loss / passes).backward()
         if timed:
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -150,7 +163,8 @@ def main():
     if rank == 0:
         print(json.dumps({
             "metric": "sequences/sec (whole node), BERT-Large bf16 pre-training, fp16 compression + Adasum",
-            "value": round(args.batch * size * args.steps / el, 2), "unit": "sequences/sec",
+            "value": round(args.batch * passes * size * args.steps / el, 2),
+            "unit": "sequences/sec",
             "n_gpus": size, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(el / args.steps * 1000, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
@@ -160,6 +174,8 @@ def main():
                        "seq_len": args.seq, "parallelism": f"dp{size}",
                        "compression": args.compression, "op": args.op,
                        "optimizer": "mivod FusedAdamW", "max_grad_norm": args.max_grad_norm,
+                       "backward_passes_per_step": passes,
+                       "accumulation_dtype": args.accumulation_dtype,
                        "transport": basics.state().backend if size > 1 else "local"},
             "comm": comm}), flush=True)
     hvd.shutdown()

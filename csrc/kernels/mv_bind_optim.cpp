@@ -1,9 +1,13 @@
 // mivod._mvk bindings: multi-tensor pack / cast, fused optimizer steps, global gradient-norm
-// clipping, Adasum (mv_kernels.h, mv_adaptive.h, mv_clip.h)
+// clipping, local gradient accumulation, Adasum (mv_kernels.h, mv_adaptive.h, mv_clip.h,
+// mv_accum.h)
+#include "mv_accum.h"
 #include "mv_adaptive.h"
 #include "mv_checks.h"
 #include "mv_clip.h"
 #include "mv_kernels.h"
+
+#include <algorithm>
 
 namespace {
 using namespace mvc;
@@ -13,6 +17,44 @@ constexpr int64_t kChunk = 4096;
 // optional int32 device flag (non-finite result / fp16-wire overflow skip)
 int* flag_ptr(const char* fn, const char* what, const OptTensor& f, const at::Tensor& like) {
   return vec_ptr_opt<int>(fn, what, f, like, 1, true);
+}
+
+// The tensor table of a multi-tensor launch: checks every tensor (dense, one dtype, on
+// `flat`'s device, [offsets[i], +numel) inside fnumel elements) and calls launch(table) once
+// per kMvMaxTensors tensors / 2^30 chunks.
+template <typename Launch>
+void mt_tables(const char* fn, const std::vector<at::Tensor>& tensors, const at::Tensor& flat,
+               const std::vector<int64_t>& offsets, int64_t fnumel, Launch launch) {
+  const int tdt = dtype_code(tensors[0]);
+  MtArgs a;
+  a.ntensors = 0;
+  a.chunk_start[0] = 0;
+  auto flush = [&]() {
+    if (a.ntensors == 0) return;
+    launch(a);
+    a.ntensors = 0;
+    a.chunk_start[0] = 0;
+  };
+  for (size_t i = 0; i < tensors.size(); ++i) {
+    const at::Tensor& t = tensors[i];
+    check_dense(fn, "tensors", t, flat, false);
+    TORCH_CHECK(dtype_code(t) == tdt, fn, ": mixed tensor dtypes in one call");
+    const int64_t n = t.numel();
+    TORCH_CHECK(offsets[i] >= 0 && offsets[i] + n <= fnumel, fn, ": tensor ", i,
+                " [", offsets[i], ", +", n, ") exceeds flat buffer of ", fnumel);
+    if (n == 0) continue;
+    const int64_t chunks = (n + kChunk - 1) / kChunk;
+    TORCH_CHECK(chunks < (1 << 30), fn, ": tensor too large");
+    if (a.ntensors == kMvMaxTensors ||
+        (int64_t)a.chunk_start[a.ntensors] + chunks > (int64_t)(1u << 30))
+      flush();
+    const int k = a.ntensors++;
+    a.ptr[k] = t.data_ptr();
+    a.numel[k] = n;
+    a.flat_off[k] = offsets[i];
+    a.chunk_start[k + 1] = a.chunk_start[k] + (int32_t)chunks;
+  }
+  flush();
 }
 
 // K1/K2: pack (to_flat) or unpack tensors <-> flat[offsets[i] : offsets[i]+numel]
@@ -26,38 +68,48 @@ void mt_copy(const std::vector<at::Tensor>& tensors, at::Tensor flat,
   c10::DeviceGuard guard(flat.device());
   const int tdt = dtype_code(tensors[0]);
   const int fdt = dtype_code(flat);
-  const int64_t fnumel = flat.numel();
   int* nf = flag_ptr("mt_copy", "nonfinite", nonfinite, flat);
   hipStream_t st = cur_stream();
-  MtArgs a;
-  a.ntensors = 0;
-  a.chunk_start[0] = 0;
-  auto flush = [&]() {
-    if (a.ntensors == 0) return;
+  mt_tables("mt_copy", tensors, flat, offsets, flat.numel(), [&](const MtArgs& a) {
     mv_launch_mt_copy(a, tdt, flat.data_ptr(), fdt, to_flat, (float)scale, nf, st);
-    a.ntensors = 0;
-    a.chunk_start[0] = 0;
-  };
-  for (size_t i = 0; i < tensors.size(); ++i) {
-    const at::Tensor& t = tensors[i];
-    check_dense("mt_copy", "tensors", t, flat, false);
-    TORCH_CHECK(dtype_code(t) == tdt, "mt_copy: mixed tensor dtypes in one call");
-    const int64_t n = t.numel();
-    TORCH_CHECK(offsets[i] >= 0 && offsets[i] + n <= fnumel, "mt_copy: tensor ", i,
-                " [", offsets[i], ", +", n, ") exceeds flat buffer of ", fnumel);
-    if (n == 0) continue;
-    const int64_t chunks = (n + kChunk - 1) / kChunk;
-    TORCH_CHECK(chunks < (1 << 30), "mt_copy: tensor too large");
-    if (a.ntensors == kMvMaxTensors ||
-        (int64_t)a.chunk_start[a.ntensors] + chunks > (int64_t)(1u << 30))
-      flush();
-    const int k = a.ntensors++;
-    a.ptr[k] = t.data_ptr();
-    a.numel[k] = n;
-    a.flat_off[k] = offsets[i];
-    a.chunk_start[k + 1] = a.chunk_start[k] + (int32_t)chunks;
-  }
-  flush();
+  });
+}
+
+// Local gradient accumulation (mv_accum.hip): acc[offsets[i] : +numel] = (first) or += float(t_i)
+void accumulate(const std::vector<at::Tensor>& tensors, at::Tensor acc,
+                const std::vector<int64_t>& offsets, bool first) {
+  TORCH_CHECK(tensors.size() == offsets.size(), "accumulate: tensors/offsets length mismatch");
+  if (tensors.empty()) return;
+  check_dense("accumulate", "tensors", tensors[0], tensors[0], false);
+  float* ap = vec_ptr("accumulate", "acc", acc, tensors[0], 0, true);
+  c10::DeviceGuard guard(acc.device());
+  const int tdt = dtype_code(tensors[0]);
+  hipStream_t st = cur_stream();
+  mt_tables("accumulate", tensors, acc, offsets, acc.numel(), [&](const MtArgs& a) {
+    mv_launch_accumulate(a, tdt, ap, first, st);
+  });
+}
+
+// dst[offsets[i] : +numel] = cast((acc[offsets[i] : +numel] + float(t_i)) * scale); acc is read
+void pack_accumulated(const std::vector<at::Tensor>& tensors, at::Tensor acc, at::Tensor dst,
+                      const std::vector<int64_t>& offsets, double scale,
+                      c10::optional<at::Tensor> nonfinite) {
+  TORCH_CHECK(tensors.size() == offsets.size(),
+              "pack_accumulated: tensors/offsets length mismatch");
+  if (tensors.empty()) return;
+  check_dense("pack_accumulated", "tensors", tensors[0], tensors[0], false);
+  check_dense("pack_accumulated", "dst", dst, tensors[0]);
+  const float* ap = vec_ptr("pack_accumulated", "acc", acc, tensors[0], 0, true);
+  c10::DeviceGuard guard(dst.device());
+  const int tdt = dtype_code(tensors[0]);
+  const int wdt = dtype_code(dst);
+  int* nf = flag_ptr("pack_accumulated", "nonfinite", nonfinite, dst);
+  hipStream_t st = cur_stream();
+  // every range must lie inside both flat buffers
+  const int64_t fnumel = std::min(acc.numel(), dst.numel());
+  mt_tables("pack_accumulated", tensors, dst, offsets, fnumel, [&](const MtArgs& a) {
+    mv_launch_pack_accumulated(a, tdt, ap, dst.data_ptr(), wdt, (float)scale, nf, st);
+  });
 }
 
 void flat_cast(at::Tensor src, at::Tensor dst, double scale, c10::optional<at::Tensor> nonfinite) {
@@ -494,6 +546,13 @@ void bind_optim(pybind11::module_& m) {
   cl.def("lamb_step", &lamb_step_clip, "lamb_step with gscale *= gclip[0] on the device");
   cl.def("rmsprop_step", &rmsprop_step_clip, "rmsprop_step with gscale *= gclip[0] on the device");
   cl.def("adagrad_step", &adagrad_step_clip, "adagrad_step with gscale *= gclip[0] on the device");
+  // and local gradient accumulation in an fp32 arena: mivod._mvk._accum
+  pybind11::module_ ac = m.def_submodule(
+      "_accum", "fp32 accumulation of backward_passes_per_step micro-batch gradients");
+  ac.def("accumulate", &accumulate,
+         "acc[off_i : off_i + n_i] = float(t_i) (first) or += float(t_i), one launch");
+  ac.def("pack_accumulated", &pack_accumulated,
+         "dst[off_i : off_i + n_i] = cast((acc[off_i : off_i + n_i] + float(t_i)) * scale)");
   m.def("seg_dot3", &seg_dot3, "per-segment (a.b, |a|^2, |b|^2) (swap: (a.b, |b|^2, |a|^2))");
   m.def("adasum_merge", &adasum_merge,
         "one vector-halving Adasum level: merge with fixed-order group Gram sums + fused wire cast");

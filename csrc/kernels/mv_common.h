@@ -1,5 +1,5 @@
 // mivod CDNA4 (gfx950) kernel helpers: dtype tags, 8-wide vector load/store
-// with fused conversion, wave64 reductions, the dropout hash, the CU count.  What only
+// with fused conversion, the scale-then-cast helpers of the flat kernels, wave64 reductions, the dropout hash, the CU count.  What only
 // the matrix-core kernels share (MFMA, LDS swizzles, transposed reads, LDS-DMA) is in
 // mv_mfma.h, which includes this header.
 //
@@ -10,6 +10,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace mv {
 
@@ -133,6 +135,26 @@ __device__ __forceinline__ void st1(T* p, float v) { *p = from_f32<T>(v); }
 
 __device__ __forceinline__ bool aligned16(const void* p) {
   return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
+}
+
+// the value as the destination dtype stores it (the non-finite check of a pack must see
+// an fp16 overflow of the cast, as the overflow guard's scan of the packed bucket would)
+template <typename TD>
+__device__ __forceinline__ float stored(float x) {
+  if constexpr (std::is_same<TD, float>::value) return x;
+  else return (float)(TD)x;
+}
+
+// x * scale rounded to fp32 before the cast to the destination dtype, as
+// (t.float() * scale).to(dst) rounds: left to the compiler, the vector body folds the
+// multiply into the f16 conversion (one rounding of the exact product), which differs from
+// the scalar paths and from PyTorch wherever the fp32 product is a tie of the destination
+// (tests/test_flat_kernels_gpu.py found 8 such elements in 4096).  The empty asm makes the
+// fp32 product a value the conversion cannot look through; it emits no instruction.
+__device__ __forceinline__ float scaled(float x, float scale) {
+  float p = x * scale;
+  asm("" : "+v"(p));
+  return p;
 }
 
 constexpr float kSqrt1_2 = 0.70710678118654752f;

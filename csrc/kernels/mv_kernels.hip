@@ -20,8 +20,6 @@
 #include "mv_flat_step.h"
 #include "mv_kernels.h"
 
-#include <type_traits>
-
 namespace mv {
 
 // -------------------------------------------------------------------------
@@ -30,26 +28,6 @@ namespace mv {
 // safe).  Workgroup b finds its tensor by a uniform binary search over the
 // chunk prefix sums (scalar loads from the kernarg segment).
 // -------------------------------------------------------------------------
-// the value as the destination dtype stores it (the non-finite check of a pack must see
-// an fp16 overflow of the cast, as the overflow guard's scan of the packed bucket would)
-template <typename TD>
-__device__ __forceinline__ float stored(float x) {
-  if constexpr (std::is_same<TD, float>::value) return x;
-  else return (float)(TD)x;
-}
-
-// x * scale rounded to fp32 before the cast to the destination dtype, as
-// (t.float() * scale).to(dst) rounds: left to the compiler, the vector body folds the
-// multiply into the f16 conversion (one rounding of the exact product), which differs from
-// the scalar paths and from PyTorch wherever the fp32 product is a tie of the destination
-// (tests/test_flat_kernels_gpu.py found 8 such elements in 4096).  The empty asm makes the
-// fp32 product a value the conversion cannot look through; it emits no instruction.
-__device__ __forceinline__ float scaled(float x, float scale) {
-  float p = x * scale;
-  asm("" : "+v"(p));
-  return p;
-}
-
 template <typename TS, typename TD>
 __device__ __forceinline__ void copy_range(const TS* __restrict__ s, TD* __restrict__ d,
                                            int64_t n, float scale, int* found_nonfinite) {

@@ -125,6 +125,59 @@ def nonfinite_scan(x: torch.Tensor, flag: torch.Tensor) -> None:
 
 
 # ---------------------------------------------------------------------------
+# Local gradient accumulation in an fp32 arena (backward_passes_per_step > 1)
+# ---------------------------------------------------------------------------
+def _check_accum(tensors, acc, offsets) -> None:
+    if len(tensors) != len(offsets):
+        raise ValueError("accumulate: tensors/offsets length mismatch")
+    if acc.dtype != torch.float32 or not acc.is_contiguous():
+        raise ValueError("accumulate: acc must be a contiguous fp32 tensor")
+
+
+def accumulate(tensors: Sequence[torch.Tensor], acc: torch.Tensor, offsets: Sequence[int],
+               first: bool) -> None:
+    """acc[off_i : off_i+n_i] = float(t_i) (``first``: a write, so the accumulator needs no
+    zeroing) or += float(t_i), in the raw memory order of t_i: one multi-tensor launch.  The
+    conversion is exact and each add rounds once to fp32.  Tensors of one call share a dtype;
+    nothing outside the ranges is touched."""
+    if not tensors:
+        return
+    _check_accum(tensors, acc, offsets)
+    if _on_gpu(acc):
+        native()._accum.accumulate(list(tensors), acc, [int(o) for o in offsets], bool(first))
+        return
+    for t, o in zip(tensors, offsets):
+        src = _raw_flat(t).float()
+        dst = acc[o:o + src.numel()]
+        if first:
+            dst.copy_(src)
+        else:
+            dst.add_(src)
+
+
+def pack_accumulated(tensors: Sequence[torch.Tensor], acc: torch.Tensor, dst: torch.Tensor,
+                     offsets: Sequence[int], scale: float = 1.0,
+                     nonfinite: Optional[torch.Tensor] = None) -> None:
+    """dst[off_i : off_i+n_i] = cast((acc[off_i : off_i+n_i] + float(t_i)) * scale): the last
+    pass of an accumulation window fused with the wire cast of ``pack``.  The fp32 sum and the
+    fp32 product are each rounded before the cast; ``acc`` is only read.  ``nonfinite``
+    (optional) |= any stored value that is not finite, as in ``pack``."""
+    if not tensors:
+        return
+    _check_accum(tensors, acc, offsets)
+    if _on_gpu(dst):
+        native()._accum.pack_accumulated(list(tensors), acc, dst, [int(o) for o in offsets],
+                                         float(scale), nonfinite)
+        return
+    for t, o in zip(tensors, offsets):
+        src = _raw_flat(t).float()
+        out = dst[o:o + src.numel()]
+        out.copy_((acc[o:o + src.numel()] + src) * scale)
+        if nonfinite is not None and not bool(torch.isfinite(out.float()).all()):
+            nonfinite.fill_(1)
+
+
+# ---------------------------------------------------------------------------
 # Global gradient-norm clipping (max_grad_norm of the Fused* optimizers)
 # ---------------------------------------------------------------------------
 def sumsq_chunks(n: int) -> int:

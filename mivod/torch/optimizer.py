@@ -55,6 +55,27 @@ MI355X design (not a translation of horovod's per-tensor async ops):
   reduced bits, so every rank clips identically with no extra collective and no
   host wait; the price is that the updates no longer overlap backward (with the
   guard in "step" mode they already do not).
+* **Local accumulation in fp32** (``backward_passes_per_step=k`` with
+  ``accumulation_dtype=torch.float32``; the default ``None`` leaves the k passes to
+  autograd's ``p.grad += g``, one small launch per parameter per pass in the
+  parameter's own dtype — an 8-bit significand for bf16 models).  Each arena gets an fp32
+  accumulator with the layout of its gradient buffer (4 bytes per parameter, allocated at
+  the first non-final pass).  When every parameter of a bucket has fired its hook for the
+  c-th time, c < k, ONE multi-tensor launch per bucket (``accumulate``: the window's first
+  launch writes, the later ones add) takes whichever ``p.grad`` are present on the compute
+  stream and ``p.grad`` is released, so gradient memory is held for one micro-pass only.
+  The k-th pass goes through the usual bucket launch with the pack replaced by
+  ``pack_accumulated``: (accumulator + gradient) * prescale, cast to the wire dtype, the
+  overflow flag set from the stored value — everything after it (collective, guard,
+  clipping, fused or plain update) is unchanged.  Horovod's semantics stay: the passes are
+  summed, not averaged; the user scales the loss.  A parameter whose hooks fire
+  irregularly (unused in some pass) delays its bucket's launch: the gradients of that
+  bucket keep accumulating in ``p.grad`` as without the option and join at the next
+  launch.  A parameter with accumulated passes but no gradient in the last one, and
+  ``synchronize()`` on a partial window, emit the accumulator through ``flat_cast``.
+  ``zero_grad()`` inside an open window discards the accumulated passes as it discards
+  ``p.grad``.  The accumulator is not part of ``state_dict()``: a checkpoint taken inside
+  a window loses the open window's passes.  See docs/ACCUMULATION.md.
 * **Timeline**: with ``HOROVOD_TIMELINE`` set, every bucket's pack / collective
   / fused step is recorded with GPU timestamps (``utils.timeline.PhaseRecorder``).
 """
@@ -120,7 +141,7 @@ class _GradArena:
 
 class _Bucket:
     __slots__ = ("index", "arena", "i0", "i1", "lo", "hi", "params", "pending", "launched",
-                 "order_key", "name")
+                 "order_key", "name", "fired", "acc_on")
 
     def __init__(self, index, arena, i0, i1, order_key):
         self.index = index
@@ -130,6 +151,10 @@ class _Bucket:
         self.params = arena.params[i0:i1]
         self.pending = len(self.params)
         self.launched = False
+        # accumulation_dtype: {c: parameters whose hook fired for the c-th time}, and whether
+        # the fp32 accumulator holds this window's passes of the bucket
+        self.fired: Dict[int, int] = {}
+        self.acc_on = False
         self.order_key = order_key
         self.name = f"bucket.{index}"
 
@@ -199,7 +224,7 @@ class _DistributedOptimizerMixin:
     # ------------------------------------------------------------------ setup
     def _mvd_setup(self, named_parameters, compression, backward_passes_per_step, op,
                    bucket_mb, first_bucket_mb, gradient_predivide_factor,
-                   overflow_guard=None, grad_scale=None):
+                   overflow_guard=None, grad_scale=None, accumulation_dtype=None):
         st = basics.state()
         if not st.initialized:
             raise ValueError(basics._NOT_INIT)
@@ -213,6 +238,13 @@ class _DistributedOptimizerMixin:
         self._mvd_rank = st.rank
         self._mvd_compression = compression
         self._mvd_bpps = int(backward_passes_per_step)
+        if accumulation_dtype not in (None, torch.float32):
+            raise ValueError("accumulation_dtype must be None (accumulate in p.grad, in the "
+                             f"parameter's dtype) or torch.float32, not {accumulation_dtype!r}")
+        self._mvd_accum_dtype = accumulation_dtype
+        # the fp32 arena only has something to do over several passes
+        self._mvd_accum = accumulation_dtype is not None and self._mvd_bpps > 1
+        self._mvd_acc: Dict[int, torch.Tensor] = {}    # id(arena) -> fp32, a.grad's layout
         self._mvd_op = op
         self._mvd_predivide = float(gradient_predivide_factor)
         if op == C.Adasum and self._mvd_predivide != 1.0:
@@ -343,6 +375,8 @@ class _DistributedOptimizerMixin:
                        self._mvd_bpps, self._mvd_guard, self._mvd_gs,
                        self._mvd_guard_mode if self._mvd_guard else "",
                        self.max_grad_norm if self._mvd_fused else None)).encode())
+        if self._mvd_accum_dtype is not None:       # default runs hash as they always did
+            h.update(repr(("accumulation_dtype", str(self._mvd_accum_dtype))).encode())
         for b in self._mvd_buckets:
             h.update(repr((str(b.arena.grad.dtype), b.hi - b.lo,
                            [(self._mvd_names[id(p)], tuple(p.shape)) for p in b.params])).encode())
@@ -352,8 +386,8 @@ class _DistributedOptimizerMixin:
             raise ValueError(
                 "mivod DistributedOptimizer: the static gradient schedule differs across ranks "
                 f"(plan hashes {sorted(set(every.tolist()))}); every rank must wrap the same "
-                "model with the same parameter order, dtypes, op, compression, max_grad_norm and "
-                "bucket settings")
+                "model with the same parameter order, dtypes, op, compression, max_grad_norm, "
+                "backward_passes_per_step, accumulation_dtype and bucket settings")
 
     # ------------------------------------------------- gradient-norm clipping
     def _mvd_clip_check(self, max_norm):
@@ -411,6 +445,12 @@ class _DistributedOptimizerMixin:
             c = self._mvd_counts.get(id(p), 0) + 1
             self._mvd_counts[id(p)] = c
             if c < self._mvd_bpps:
+                if self._mvd_accum:
+                    b, _ = self._mvd_where[id(p)]
+                    n = b.fired.get(c, 0) + 1
+                    b.fired[c] = n
+                    if n == len(b.params):
+                        self._mvd_accumulate(b)
                 return
             if c > self._mvd_bpps:
                 raise AssertionError(
@@ -420,6 +460,53 @@ class _DistributedOptimizerMixin:
             b.pending -= 1
             if b.pending == 0 and not self._mvd_inline:
                 self._mvd_launch_ready()
+
+    # ------------------------------------------- fp32 accumulation (accumulation_dtype)
+    def _mvd_acc_of(self, a) -> torch.Tensor:
+        """The arena's fp32 accumulator: a.grad's layout, allocated on first use, zero
+        initialised; the alignment gaps are never written, so they stay zero."""
+        acc = self._mvd_acc.get(id(a))
+        if acc is None:
+            acc = torch.zeros(a.grad.numel(), dtype=torch.float32, device=a.grad.device)
+            self._mvd_acc[id(a)] = acc
+        return acc
+
+    @staticmethod
+    def _mvd_kernel_grad(p, g):
+        """``g`` as the multi-tensor kernels take it: dense, in p's memory order."""
+        if g.is_sparse:
+            g = g.to_dense()                  # sparse_as_dense (embedding grads)
+        if g.stride() != p.stride() or not K.is_dense(g):
+            g = torch.empty_like(p, dtype=g.dtype).copy_(g)
+        return g
+
+    def _mvd_accumulate(self, b: _Bucket):
+        """A non-final pass of bucket ``b`` (every parameter's hook has fired for the c-th
+        time, c < backward_passes_per_step): one multi-tensor launch per gradient dtype adds
+        whichever p.grad are present into the fp32 accumulator on the compute stream (the
+        window's first launch writes instead, and zeroes the slot of an absent gradient), and
+        p.grad is released."""
+        a = b.arena
+        acc = self._mvd_acc_of(a)
+        first = not b.acc_on
+        groups: Dict[torch.dtype, tuple] = {}
+        with torch.no_grad():
+            for k, p in enumerate(b.params):
+                lo = a.offsets[b.i0 + k]
+                g = p.grad
+                if g is None:
+                    if first:
+                        acc[lo:lo + p.numel()].zero_()
+                    continue
+                ent = groups.setdefault(g.dtype, ([], []))
+                ent[0].append(self._mvd_kernel_grad(p, g))
+                ent[1].append(lo)
+            with MK.range(f"mivod.accum.{b.name}"):
+                for gl, ol in groups.values():
+                    K.accumulate(gl, acc, ol, first)
+            for p in b.params:
+                p.grad = None                 # freed on the compute stream after the launch
+        b.acc_on = True
 
     def _mvd_launch_ready(self):
         bs = self._mvd_buckets
@@ -548,18 +635,28 @@ class _DistributedOptimizerMixin:
         groups: Dict[torch.dtype, tuple] = {}
         missing = []
         inplace = False
+        # the window's earlier passes of this bucket, when they are in the fp32 accumulator
+        acc = self._mvd_acc_of(a) if b.acc_on else None
+        from_acc = []                         # slots emitted from the accumulator alone
         with torch.no_grad():
             for k, p in enumerate(b.params):
                 i = b.i0 + k
                 g = p.grad
                 lo = a.offsets[i]
                 if g is None:
-                    missing.append((lo, p.numel()))
+                    (missing if acc is None else from_acc).append((lo, p.numel()))
                     continue
                 if g.is_sparse:
                     g = g.to_dense()          # sparse_as_dense (embedding grads)
                 if g.data_ptr() == a.grad.data_ptr() + lo * a.grad.element_size() and \
                         g.dtype == a.grad.dtype and g.stride() == p.stride():
+                    if acc is not None:
+                        # the gradient lives in its own slot of a.grad, which the last-pass
+                        # kernel would read and write through two restrict pointers: add it
+                        # to the accumulator and emit the slot from there
+                        K.accumulate([g], acc, [lo], False)
+                        from_acc.append((lo, p.numel()))
+                        continue
                     if prescale != 1.0:
                         g.mul_(prescale)
                     inplace = True
@@ -600,6 +697,10 @@ class _DistributedOptimizerMixin:
                     dst, base = a.grad, 0
                 for lo, n in missing:
                     dst[lo - base:lo - base + n].zero_()
+                if acc is not None and not groups:
+                    # no gradient at all (synchronize() on a partial window): the whole
+                    # bucket in one launch; the accumulator's gaps are zeros
+                    from_acc = [(b.lo, b.hi - b.lo)]
                 # one rank, no collective: the packed bucket IS the reduced bucket, so the
                 # overflow guard's check rides in the pack kernel (the values it writes)
                 # instead of a second pass over the bucket — unless some gradient already
@@ -608,10 +709,19 @@ class _DistributedOptimizerMixin:
                 nf = self._mvd_bucket_flag(b) if scan_in_pack else None
                 with MK.range(f"mivod.pack.{b.name}"):
                     for dt, (gl, ol) in groups.items():
-                        K.pack(gl, dst, [o - base for o in ol], scale=prescale, nonfinite=nf)
+                        if acc is None:
+                            K.pack(gl, dst, [o - base for o in ol], scale=prescale, nonfinite=nf)
+                        else:
+                            # the last pass: (accumulator + gradient) * prescale -> wire
+                            K.pack_accumulated(gl, acc[base:base + dst.numel()], dst,
+                                               [o - base for o in ol], scale=prescale,
+                                               nonfinite=nf)
+                    for lo, n in from_acc:
+                        K.flat_cast(acc[lo:lo + n], dst[lo - base:lo - base + n], prescale, nf)
                 if self._mvd_fused:
                     for p in b.params:
                         p.grad = None            # freed on the compute stream after the pack
+                b.acc_on = False                 # the next window's first pass overwrites it
             t_packed = None
             if rec is not None:
                 t_packed = rec.event() if flat.is_cuda else rec.host()
@@ -787,6 +897,7 @@ class _DistributedOptimizerMixin:
             for b in self._mvd_buckets:
                 b.launched = False
                 b.pending = len(b.params)
+                b.fired.clear()
             self._mvd_counts.clear()
             self._mvd_next = 0
             self._mvd_in_step = False
@@ -854,6 +965,10 @@ class _DistributedOptimizerMixin:
             raise AssertionError("optimizer.zero_grad() was called after loss.backward() but before "
                                  "optimizer.step() or optimizer.synchronize(). This is prohibited "
                                  "as it can cause a race condition.")
+        # inside an open accumulation window: the passes in the fp32 accumulator go the way
+        # of the ones in p.grad (the hook counters keep counting, as they always did)
+        for b in getattr(self, "_mvd_buckets", ()):
+            b.acc_on = False
         return super().zero_grad(set_to_none=set_to_none)
 
     def bucket_plan(self):
@@ -870,7 +985,7 @@ class _DoneEvent:
 def DistributedOptimizer(optimizer, named_parameters=None, compression=None,
                          backward_passes_per_step: int = 1, op=C.Average, bucket_mb=None,
                          first_bucket_mb=None, gradient_predivide_factor: float = 1.0,
-                         overflow_guard=None, grad_scale=None):
+                         overflow_guard=None, grad_scale=None, accumulation_dtype=None):
     """Wrap ``optimizer`` so gradients are averaged (``op``) across all ranks.
 
     ``compression`` defaults to ``MIVOD_COMPRESSION`` (``none``).  With an fp16
@@ -879,6 +994,15 @@ def DistributedOptimizer(optimizer, named_parameters=None, compression=None,
     A ``mivod.optim.Fused*`` optimizer's ``max_grad_norm`` clips the global norm of
     the averaged gradient (see module doc); it must agree across ranks and cannot be
     combined with ``MIVOD_GUARD_MODE=bucket``.
+
+    ``accumulation_dtype=torch.float32`` sums the ``backward_passes_per_step`` micro-batch
+    gradients in an fp32 flat accumulator (one launch per bucket per pass, ``p.grad``
+    released after every pass) instead of in ``p.grad``; ``None`` (default) keeps autograd's
+    accumulation, any other value raises ``ValueError``; with one pass per step it has no
+    effect.  It must agree across ranks.  Parameters whose hooks fire irregularly keep
+    accumulating in ``p.grad`` until their bucket's next launch; the accumulator is not
+    saved by ``state_dict()``, so a checkpoint taken inside a window loses the open window
+    (see module doc).
 
     Returns an instance of a dynamically created subclass of the optimizer's
     class (same class name, so ``isinstance`` and pickled configs keep working),
@@ -891,5 +1015,6 @@ def DistributedOptimizer(optimizer, named_parameters=None, compression=None,
     obj = cls.__new__(cls)
     obj.__dict__.update(optimizer.__dict__)
     obj._mvd_setup(named_parameters, compression, backward_passes_per_step, op, bucket_mb,
-                   first_bucket_mb, gradient_predivide_factor, overflow_guard, grad_scale)
+                   first_bucket_mb, gradient_predivide_factor, overflow_guard, grad_scale,
+                   accumulation_dtype)
     return obj
