@@ -1,7 +1,8 @@
 // mivod._mvk bindings: multi-tensor pack / cast, fused optimizer steps, global gradient-norm
-// clipping, local gradient accumulation, Adasum (mv_kernels.h, mv_adaptive.h, mv_clip.h,
-// mv_accum.h)
+// clipping, local gradient accumulation, Adasum (mv_kernels.h, mv_adaptive.h, mv_adamfam.h,
+// mv_clip.h, mv_accum.h)
 #include "mv_accum.h"
+#include "mv_adamfam.h"
 #include "mv_adaptive.h"
 #include "mv_checks.h"
 #include "mv_clip.h"
@@ -132,8 +133,8 @@ void nonfinite_scan(at::Tensor x, at::Tensor flag) {
 // sgd_step / adam_step / adadelta_step refuse an operand that is not 16-byte aligned.  Their
 // kernels (on mv_flat_step.h's skeleton, which guards its vector body) would take an offset
 // view, but the binding keeps refusing one: the arenas hand all three 64-element-aligned
-// slices, that is their contract and the existing behaviour.  LARS, LAMB, RMSprop and Adagrad
-// take any offset.
+// slices, that is their contract and the existing behaviour.  LARS, LAMB, RMSprop, Adagrad and
+// the mivod._mvk._adamfam steps take any offset.
 void check_aligned16(const char* fn, const char* what, const void* p) {
   TORCH_CHECK((reinterpret_cast<uintptr_t>(p) & 15u) == 0, fn, ": ", what,
               " must be 16-byte aligned");
@@ -419,6 +420,63 @@ void adagrad_step_clip(at::Tensor g, at::Tensor w, at::Tensor sum, c10::optional
   adagrad_impl(g, w, sum, model, lr, eps, wd, gscale, dyn, skip, gclip);
 }
 
+// Adam with amsgrad, Adamax and NAdam (mv_adamfam.hip).  One entry point each: dyn, skip and
+// gclip are trailing optional operands.
+void adam_amsgrad_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v, at::Tensor vmax,
+                       c10::optional<at::Tensor> model, double lr, double b1, double b2, double eps,
+                       double wd, double gscale, int64_t step, bool adamw, bool keras_eps,
+                       c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip,
+                       c10::optional<at::Tensor> gclip) {
+  const char* fn = "adam_amsgrad_step";
+  const StepArgs s = step_args(fn, g, w, model, dyn, skip, gclip, false);
+  float* mp = vec_ptr(fn, "exp_avg", m, g, g.numel());
+  float* vp = vec_ptr(fn, "exp_avg_sq", v, g, g.numel());
+  float* xp = vec_ptr(fn, "max_exp_avg_sq", vmax, g, g.numel());
+  TORCH_CHECK(step >= 1, fn, ": step must be >= 1");
+  const double bc1 = 1.0 - std::pow(b1, (double)step);
+  const double bc2 = 1.0 - std::pow(b2, (double)step);
+  c10::DeviceGuard guard(g.device());
+  mv_launch_adam_amsgrad(g.data_ptr(), dtype_code(g), s.w, mp, vp, xp, s.model, s.model_dt,
+                         g.numel(), (float)lr, b1, b2, (float)eps, (float)wd, (float)gscale,
+                         (float)bc1, (float)bc2, adamw, keras_eps, s.dyn, s.skip, s.gclip,
+                         cur_stream());
+}
+
+void adamax_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor u,
+                 c10::optional<at::Tensor> model, double lr, double b1, double b2, double eps,
+                 double wd, double gscale, int64_t step, bool keras_eps,
+                 c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip,
+                 c10::optional<at::Tensor> gclip) {
+  const char* fn = "adamax_step";
+  const StepArgs s = step_args(fn, g, w, model, dyn, skip, gclip, false);
+  float* mp = vec_ptr(fn, "exp_avg", m, g, g.numel());
+  float* up = vec_ptr(fn, "exp_inf", u, g, g.numel());
+  TORCH_CHECK(step >= 1, fn, ": step must be >= 1");
+  const double bc1 = 1.0 - std::pow(b1, (double)step);
+  c10::DeviceGuard guard(g.device());
+  mv_launch_adamax(g.data_ptr(), dtype_code(g), s.w, mp, up, s.model, s.model_dt, g.numel(),
+                   (float)lr, b1, b2, (float)eps, (float)wd, (float)gscale, (float)bc1, keras_eps,
+                   s.dyn, s.skip, s.gclip, cur_stream());
+}
+
+// cg = (1 - mu_t) / (1 - P_t), cm = mu_{t+1} / (1 - P_t mu_{t+1}) and bc2 = 1 - b2^t come from
+// the caller, which owns the momentum schedule; each is rounded to fp32 once here.
+void nadam_step(at::Tensor g, at::Tensor w, at::Tensor m, at::Tensor v,
+                c10::optional<at::Tensor> model, double lr, double b1, double b2, double eps,
+                double wd, double gscale, double cg, double cm, double bc2, bool adamw,
+                c10::optional<at::Tensor> dyn, c10::optional<at::Tensor> skip,
+                c10::optional<at::Tensor> gclip) {
+  const char* fn = "nadam_step";
+  const StepArgs s = step_args(fn, g, w, model, dyn, skip, gclip, false);
+  float* mp = vec_ptr(fn, "exp_avg", m, g, g.numel());
+  float* vp = vec_ptr(fn, "exp_avg_sq", v, g, g.numel());
+  TORCH_CHECK(bc2 > 0.0, fn, ": bc2 must be > 0");
+  c10::DeviceGuard guard(g.device());
+  mv_launch_nadam(g.data_ptr(), dtype_code(g), s.w, mp, vp, s.model, s.model_dt, g.numel(),
+                  (float)lr, b1, b2, (float)eps, (float)wd, (float)gscale, (float)cg, (float)cm,
+                  (float)bc2, adamw, s.dyn, s.skip, s.gclip, cur_stream());
+}
+
 // Global gradient-norm clipping (mv_clip.hip).  grad_sumsq writes one fp32 partial per
 // 4096-element chunk of x; clip_finalize turns partial[0:total) into clip = [coef, norm].
 void grad_sumsq(at::Tensor x, at::Tensor partial, c10::optional<at::Tensor> flag) {
@@ -530,6 +588,13 @@ void bind_optim(pybind11::module_& m) {
       "_adaptive", "RMSprop and Adagrad steps on the flat-arena path");
   ad.def("rmsprop_step", &rmsprop_step, "fused flat RMSprop step (centered / momentum optional)");
   ad.def("adagrad_step", &adagrad_step, "fused flat Adagrad step");
+  // and the rest of the Adam family: mivod._mvk._adamfam (dyn, skip and gclip all optional)
+  pybind11::module_ af = m.def_submodule(
+      "_adamfam", "Adam with amsgrad, Adamax and NAdam steps on the flat-arena path");
+  af.def("adam_amsgrad_step", &adam_amsgrad_step,
+         "fused flat Adam/AdamW step with amsgrad (max_exp_avg_sq in the denominator)");
+  af.def("adamax_step", &adamax_step, "fused flat Adamax step");
+  af.def("nadam_step", &nadam_step, "fused flat NAdam step");
   // and global gradient-norm clipping: mivod._mvk._clip, the norm kernels and every step with
   // the device clip coefficient as one more trailing operand
   pybind11::module_ cl = m.def_submodule(

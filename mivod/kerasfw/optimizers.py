@@ -8,7 +8,8 @@ explains why the reference must keep Keras on that path); ``get_config`` /
 ``from_config`` drive re-instantiation and ``load_model``.
 
 The update itself is a mivod fused kernel (FusedAdadelta / FusedAdam with
-Keras epsilon placement / FusedSGD / FusedRMSprop / FusedAdagrad): one launch
+Keras epsilon placement, amsgrad included / FusedSGD / FusedRMSprop / FusedAdagrad /
+FusedAdamax with Keras epsilon placement / FusedNAdam): one launch
 per arena on the GPU, the plain-PyTorch reference math on the CPU.  RMSprop and
 Adagrad keep torch's form (epsilon outside the root; RMSprop's rate outside its
 momentum buffer): see their docstrings for what that changes against tf.keras.
@@ -164,14 +165,51 @@ class Adam(Optimizer):
         super().__init__(name=name, decay=decay, **kw)
         self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
         self.epsilon = float(epsilon if epsilon is not None else 1e-7)
-        if amsgrad:
-            raise NotImplementedError("amsgrad is not supported by mivod's fused Adam")
-        self.amsgrad = False
+        self.amsgrad = bool(amsgrad)
 
     def _make_impl(self, params):
         from ..optim import FusedAdam
         return FusedAdam(params, lr=float(self.lr), betas=(self.beta_1, self.beta_2),
-                         eps=self.epsilon, keras_eps=True)
+                         eps=self.epsilon, keras_eps=True, amsgrad=self.amsgrad)
+
+
+class Adamax(Optimizer):
+    """Adamax on ``FusedAdamax`` with Keras' epsilon placement: the infinity norm is
+    max(beta_2 u, |g|) and epsilon joins it in the divisor."""
+    _default_lr = 0.002
+    _hyper = ("beta_1", "beta_2", "epsilon")
+
+    def __init__(self, lr=None, beta_1=0.9, beta_2=0.999, epsilon=None, decay=0.0, name=None,
+                 **kw):
+        kw.setdefault("lr", lr if lr is not None else self._default_lr)
+        super().__init__(name=name, decay=decay, **kw)
+        self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
+        self.epsilon = float(epsilon if epsilon is not None else 1e-7)
+
+    def _make_impl(self, params):
+        from ..optim import FusedAdamax
+        return FusedAdamax(params, lr=float(self.lr), betas=(self.beta_1, self.beta_2),
+                           eps=self.epsilon, keras_eps=True)
+
+
+class Nadam(Optimizer):
+    """Nadam on ``FusedNAdam`` (torch.optim.NAdam's rule, which is Keras 2's):
+    ``schedule_decay`` is its ``momentum_decay``."""
+    _default_lr = 0.002
+    _hyper = ("beta_1", "beta_2", "epsilon", "schedule_decay")
+
+    def __init__(self, lr=None, beta_1=0.9, beta_2=0.999, epsilon=None, schedule_decay=0.004,
+                 decay=0.0, name=None, **kw):
+        kw.setdefault("lr", lr if lr is not None else self._default_lr)
+        super().__init__(name=name, decay=decay, **kw)
+        self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
+        self.epsilon = float(epsilon if epsilon is not None else 1e-7)
+        self.schedule_decay = float(schedule_decay)
+
+    def _make_impl(self, params):
+        from ..optim import FusedNAdam
+        return FusedNAdam(params, lr=float(self.lr), betas=(self.beta_1, self.beta_2),
+                          eps=self.epsilon, momentum_decay=self.schedule_decay)
 
 
 class Adadelta(Optimizer):
@@ -240,7 +278,7 @@ class Adagrad(Optimizer):
 
 
 OPTIMIZERS = {"SGD": SGD, "Adam": Adam, "Adadelta": Adadelta, "RMSprop": RMSprop,
-              "Adagrad": Adagrad}
+              "Adagrad": Adagrad, "Adamax": Adamax, "Nadam": Nadam}
 
 
 def get(opt):

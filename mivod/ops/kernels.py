@@ -419,6 +419,111 @@ def adagrad_step(g, w, sum, model, *, lr, eps=1e-10, weight_decay=0.0, gscale=1.
         model.copy_(w)
 
 
+# ---- the rest of the Adam family (csrc/kernels/mv_adamfam.hip): amsgrad, Adamax, NAdam ----
+def _adam_moments(g, w, m, v, beta1, beta2, weight_decay, gscale, coupled):
+    """gr = g * gscale (+ wd * w), m = b1 m + (1-b1) gr and, with ``v``, v = b2 v + (1-b2) gr^2
+    in place, in the kernels' order; returns gr."""
+    gr = g.float() * gscale
+    if coupled and weight_decay:
+        gr = gr + weight_decay * w
+    m.mul_(beta1).add_(gr, alpha=1 - beta1)
+    if v is not None:
+        v.mul_(beta2).addcmul_(gr, gr, value=1 - beta2)
+    return gr
+
+
+def adam_amsgrad_step(g, w, m, v, vmax, model, *, lr, beta1=0.9, beta2=0.999, eps=1e-8,
+                      weight_decay=0.0, gscale=1.0, step=1, adamw=False, keras_eps=False,
+                      dyn=None, skip=None, gclip=None):
+    """``adam_step`` with amsgrad: vmax = max(vmax, v), taken on the uncorrected v as torch and
+    Keras take it, replaces v in the denominator (either epsilon placement).  ``dyn`` (GPU
+    only) = [lr, -, bc1, bc2]."""
+    if _on_gpu(g):
+        native()._adamfam.adam_amsgrad_step(
+            g, w, m, v, vmax, model, float(lr), float(beta1), float(beta2), float(eps),
+            float(weight_decay), float(gscale), int(step), bool(adamw), bool(keras_eps), dyn, skip,
+            gclip)
+        return
+    if _skipped(skip):
+        return
+    gscale = _clipped(gscale, gclip)
+    _adam_moments(g, w, m, v, beta1, beta2, weight_decay, gscale, not adamw)
+    torch.maximum(vmax, v, out=vmax)
+    bc1 = 1 - beta1 ** step
+    bc2 = 1 - beta2 ** step
+    if adamw and weight_decay:
+        w.mul_(1 - lr * weight_decay)
+    if keras_eps:
+        denom = (vmax.sqrt() + eps) / math.sqrt(bc2)
+    else:
+        denom = vmax.sqrt() / math.sqrt(bc2) + eps
+    w.addcdiv_(m, denom, value=-lr / bc1)
+    if model is not None:
+        model.copy_(w)
+
+
+def adamax_step(g, w, m, u, model, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+                gscale=1.0, step=1, keras_eps=False, dyn=None, skip=None, gclip=None):
+    """Adamax with torch.optim.Adamax's semantics: gr = g * gscale + wd * w,
+    m = b1 m + (1-b1) gr, u = max(b2 u, |gr| + eps), w -= lr / (1 - b1^step) * m / u.
+    ``keras_eps``: Keras' placement, u = max(b2 u, |gr|) and the divisor u + eps.  One deviation
+    from torch: an element whose divisor is exactly 0 (eps = 0 and an all-zero history) takes no
+    update, where torch's 0/0 is NaN.  ``dyn`` (GPU only) = [lr, -, bc1, -]."""
+    if _on_gpu(g):
+        native()._adamfam.adamax_step(
+            g, w, m, u, model, float(lr), float(beta1), float(beta2), float(eps),
+            float(weight_decay), float(gscale), int(step), bool(keras_eps), dyn, skip, gclip)
+        return
+    if _skipped(skip):
+        return
+    gscale = _clipped(gscale, gclip)
+    gr = _adam_moments(g, w, m, None, beta1, beta2, weight_decay, gscale, True)
+    a = gr.abs()
+    torch.maximum(u.mul_(beta2), a if keras_eps else a.add_(eps), out=u)
+    d = u + eps if keras_eps else u
+    q = (lr / (1 - beta1 ** step)) * m / d
+    w.sub_(torch.where(d != 0, q, torch.zeros_like(q)))
+    if model is not None:
+        model.copy_(w)
+
+
+def nadam_coefficients(mu, mu_next, mu_product):
+    """(cg, cm) of a NAdam step from mu_t, mu_{t+1} and P_t = mu_1 ... mu_t, in double: the
+    weight of the gradient, (1 - mu_t) / (1 - P_t), and of the first moment,
+    mu_{t+1} / (1 - P_t mu_{t+1})."""
+    return (1.0 - mu) / (1.0 - mu_product), mu_next / (1.0 - mu_product * mu_next)
+
+
+def nadam_mu(step, beta1, momentum_decay):
+    """mu_step = beta1 (1 - 0.5 * 0.96^(step * momentum_decay)) of torch.optim.NAdam."""
+    return beta1 * (1.0 - 0.5 * (0.96 ** (step * momentum_decay)))
+
+
+def nadam_step(g, w, m, v, model, *, lr, cg, cm, bc2, beta1=0.9, beta2=0.999, eps=1e-8,
+               weight_decay=0.0, gscale=1.0, adamw=False, dyn=None, skip=None, gclip=None):
+    """NAdam with torch.optim.NAdam's semantics: m and v as in Adam,
+    denom = sqrt(v / bc2) + eps, w -= lr cg gr / denom + lr cm m / denom with ``cg``, ``cm``
+    (``nadam_coefficients``) and ``bc2`` = 1 - b2^step taken by the caller in double.
+    ``adamw``: decoupled weight decay, w *= 1 - lr wd, instead of the coupled + wd w.
+    ``dyn`` (GPU only) = [lr, cg, cm, bc2]."""
+    if _on_gpu(g):
+        native()._adamfam.nadam_step(
+            g, w, m, v, model, float(lr), float(beta1), float(beta2), float(eps),
+            float(weight_decay), float(gscale), float(cg), float(cm), float(bc2), bool(adamw), dyn,
+            skip, gclip)
+        return
+    if _skipped(skip):
+        return
+    gscale = _clipped(gscale, gclip)
+    gr = _adam_moments(g, w, m, v, beta1, beta2, weight_decay, gscale, not adamw)
+    if adamw and weight_decay:
+        w.mul_(1 - lr * weight_decay)
+    denom = v.sqrt() / math.sqrt(bc2) + eps
+    w.sub_(((lr * cg) * gr + (lr * cm) * m) / denom)
+    if model is not None:
+        model.copy_(w)
+
+
 # ---------------------------------------------------------------------------
 # Segment / chunk tables (LARS, Adasum)
 # ---------------------------------------------------------------------------

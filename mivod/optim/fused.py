@@ -43,6 +43,31 @@ def check_max_grad_norm(v):
     return f
 
 
+def dyn_values(a) -> List[float]:
+    """[lr, first, bc1, bc2] of arena ``a`` for its current ``a.step``: the device
+    hyperparameter block of a HIP-graph replay (mivod.torch.graphs)."""
+    g = a.group
+    bc1 = bc2 = 1.0
+    betas = g.get("betas")
+    if betas is not None:
+        bc1 = 1.0 - float(betas[0]) ** a.step
+        bc2 = 1.0 - float(betas[1]) ** a.step
+    return [float(g["lr"]), 1.0 if a.step == 1 else 0.0, bc1, bc2]
+
+
+def _check_adam_ranges(name, lr, betas, eps, weight_decay):
+    if not 0.0 <= lr:
+        raise ValueError(f"{name}: invalid learning rate: {lr}")
+    if not 0.0 <= eps:
+        raise ValueError(f"{name}: invalid epsilon value: {eps}")
+    if not 0.0 <= betas[0] < 1.0:
+        raise ValueError(f"{name}: invalid beta parameter at index 0: {betas[0]}")
+    if not 0.0 <= betas[1] < 1.0:
+        raise ValueError(f"{name}: invalid beta parameter at index 1: {betas[1]}")
+    if not 0.0 <= weight_decay:
+        raise ValueError(f"{name}: invalid weight_decay value: {weight_decay}")
+
+
 class Arena:
     """A flat arena for the params of one (param_group, dtype)."""
 
@@ -207,6 +232,12 @@ class FusedOptimizer(torch.optim.Optimizer):
             a.dyn = torch.zeros(4, dtype=torch.float32, device=a.device)
         return a.dyn
 
+    def _mv_dyn_values(self, a: Arena) -> List[float]:
+        """The four floats a HIP-graph replay writes into ``a.dyn`` before it launches, for
+        the arena's current ``a.step``: [lr, first, bc1, bc2] unless the optimizer's kernel
+        reads its block differently."""
+        return dyn_values(a)
+
     def _mv_slices(self, a: Arena, i0: int, i1: int):
         lo, hi = a.range_of(i0, i1)
         model = a.model[lo:hi] if a.low_precision else None
@@ -304,6 +335,11 @@ class FusedOptimizer(torch.optim.Optimizer):
                 if k in state_dict.get("state", {}):
                     raw[p] = state_dict["state"][k]
         super().load_state_dict(state_dict)
+        # a torch.optim state dict brings torch's group keys: ours that it lacks keep their
+        # constructor values
+        for g in self.param_groups:
+            for k, v in self.defaults.items():
+                g.setdefault(k, v)
         # torch replaced our views with fresh tensors: copy them back into the arenas
         with torch.no_grad():
             for a in arenas:
@@ -353,31 +389,46 @@ class FusedSGD(FusedOptimizer):
 
 class FusedAdam(FusedOptimizer):
     """Adam / AdamW.  ``keras_eps=True`` uses Keras' epsilon placement
-    (eps scaled by sqrt(1-beta2^t)), matching tf.optimizers.Adam."""
+    (eps scaled by sqrt(1-beta2^t)), matching tf.optimizers.Adam.
+
+    ``amsgrad=True`` keeps the running maximum of the second moment in a third state stream,
+    ``max_exp_avg_sq`` (torch's name, so a ``torch.optim.Adam(amsgrad=True)`` state dict
+    loads), and divides by it: the maximum is taken on the uncorrected moment, as torch and
+    Keras take it.  It decides which state arenas exist, so it is fixed at construction; the
+    ``amsgrad`` entry of a param group is informational."""
 
     _state_names = ["exp_avg", "exp_avg_sq"]
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 adamw=False, keras_eps=False, grad_dtype=None, max_grad_norm=None):
+                 adamw=False, keras_eps=False, grad_dtype=None, max_grad_norm=None,
+                 amsgrad=False):
+        _check_adam_ranges(type(self).__name__, lr, betas, eps, weight_decay)
+        self._mv_amsgrad = bool(amsgrad)
+        if self._mv_amsgrad:
+            self._state_names = ["exp_avg", "exp_avg_sq", "max_exp_avg_sq"]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      adamw=adamw, keras_eps=keras_eps), grad_dtype,
-                         max_grad_norm)
+                                      adamw=adamw, keras_eps=keras_eps,
+                                      amsgrad=self._mv_amsgrad), grad_dtype, max_grad_norm)
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
         g, w, st, model = self._mv_slices(a, i0, i1)
         hp = a.group
         b1, b2 = hp["betas"]
-        K.adam_step(g, w, st["exp_avg"], st["exp_avg_sq"], model, lr=hp["lr"], beta1=b1, beta2=b2,
-                    eps=hp["eps"], weight_decay=hp["weight_decay"], gscale=gscale, step=a.step,
-                    adamw=hp["adamw"], keras_eps=hp["keras_eps"], dyn=self._mv_dyn(a),
-                    skip=self._mv_skip, gclip=self._mv_clip)
+        kw = dict(lr=hp["lr"], beta1=b1, beta2=b2, eps=hp["eps"], weight_decay=hp["weight_decay"],
+                  gscale=gscale, step=a.step, adamw=hp["adamw"], keras_eps=hp["keras_eps"],
+                  dyn=self._mv_dyn(a), skip=self._mv_skip, gclip=self._mv_clip)
+        if self._mv_amsgrad:
+            K.adam_amsgrad_step(g, w, st["exp_avg"], st["exp_avg_sq"], st["max_exp_avg_sq"], model,
+                                **kw)
+        else:
+            K.adam_step(g, w, st["exp_avg"], st["exp_avg_sq"], model, **kw)
 
 
 class FusedAdamW(FusedAdam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 grad_dtype=None, max_grad_norm=None):
+                 grad_dtype=None, max_grad_norm=None, amsgrad=False):
         super().__init__(params, lr, betas, eps, weight_decay, adamw=True, grad_dtype=grad_dtype,
-                         max_grad_norm=max_grad_norm)
+                         max_grad_norm=max_grad_norm, amsgrad=amsgrad)
 
 
 class FusedAdadelta(FusedOptimizer):
@@ -528,3 +579,106 @@ class FusedAdagrad(FusedOptimizer):
         K.adagrad_step(g, w, st["sum"], model, lr=clr, eps=hp["eps"],
                        weight_decay=hp["weight_decay"], gscale=gscale, dyn=self._mv_dyn(a),
                        skip=self._mv_skip, gclip=self._mv_clip)
+
+
+class FusedAdamax(FusedOptimizer):
+    """Adamax (Kingma & Ba 2015, section 7) with torch.optim.Adamax's semantics and state names
+    (``exp_avg``, ``exp_inf``), so a torch.optim.Adamax state dict loads: with
+    gr = g + weight_decay * w, exp_avg = b1 exp_avg + (1-b1) gr,
+    exp_inf = max(b2 exp_inf, |gr| + eps) and w -= lr / (1 - b1^t) * exp_avg / exp_inf.
+    ``keras_eps=True`` uses Keras' epsilon placement: exp_inf = max(b2 exp_inf, |gr|) and the
+    divisor exp_inf + eps.  Weight decay is the coupled one only.  One deviation from torch:
+    an element whose divisor is exactly 0 (``eps=0`` and a gradient history of zeros) takes no
+    update, where torch divides 0 by 0 and stores NaN."""
+
+    _state_names = ["exp_avg", "exp_inf"]
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 keras_eps=False, grad_dtype=None, max_grad_norm=None):
+        _check_adam_ranges("FusedAdamax", lr, betas, eps, weight_decay)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      keras_eps=bool(keras_eps)), grad_dtype, max_grad_norm)
+
+    def _mv_apply(self, a, i0, i1, gscale=1.0):
+        g, w, st, model = self._mv_slices(a, i0, i1)
+        hp = a.group
+        b1, b2 = hp["betas"]
+        K.adamax_step(g, w, st["exp_avg"], st["exp_inf"], model, lr=hp["lr"], beta1=b1, beta2=b2,
+                      eps=hp["eps"], weight_decay=hp["weight_decay"], gscale=gscale, step=a.step,
+                      keras_eps=hp["keras_eps"], dyn=self._mv_dyn(a), skip=self._mv_skip,
+                      gclip=self._mv_clip)
+
+
+class FusedNAdam(FusedOptimizer):
+    """NAdam (Dozat 2016) with torch.optim.NAdam's semantics and state names (``exp_avg``,
+    ``exp_avg_sq``), which is also Keras ``Nadam``'s rule: with
+    mu_t = b1 (1 - 0.5 * 0.96^(t * momentum_decay)) and P_t = mu_1 ... mu_t,
+    w -= lr (1-mu_t)/(1-P_t) gr / denom + lr mu_{t+1}/(1 - P_t mu_{t+1}) exp_avg / denom,
+    denom = sqrt(exp_avg_sq / (1 - b2^t)) + eps.  ``decoupled_weight_decay=True`` decays the
+    weights by 1 - lr * weight_decay instead of adding weight_decay * w to the gradient.
+
+    The two weights and the bias correction are taken on the host in double and handed to the
+    kernel (or, under a captured HIP graph, written into its device block [lr, cg, cm, bc2]).
+    P_t is not stored: it is derived from the arena's step count and the group's CURRENT
+    ``betas[0]`` and ``momentum_decay`` (cached incrementally), so ``load_state_dict`` and a
+    graph capture's rollback of the step count need nothing more.  The consequence: a ``beta1``
+    or ``momentum_decay`` changed in the middle of training re-derives the whole product with
+    the new value, where torch keeps the product of the values each step was taken with.
+    ``state_dict()`` exposes the product per parameter as ``mu_product``, torch's entry; on
+    loading it is ignored in favour of the derived one."""
+
+    _state_names = ["exp_avg", "exp_avg_sq"]
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 momentum_decay=4e-3, decoupled_weight_decay=False, grad_dtype=None,
+                 max_grad_norm=None):
+        _check_adam_ranges("FusedNAdam", lr, betas, eps, weight_decay)
+        if not 0.0 <= momentum_decay:
+            raise ValueError(f"FusedNAdam: invalid momentum_decay value: {momentum_decay}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      momentum_decay=momentum_decay,
+                                      decoupled_weight_decay=bool(decoupled_weight_decay)),
+                         grad_dtype, max_grad_norm)
+        self._mv_mu_key = None
+        self._mv_mu_products = [1.0]      # P_0 .. P_t for _mv_mu_key = (beta1, momentum_decay)
+
+    def mu_product(self, step: int, beta1: float, momentum_decay: float) -> float:
+        """P_step = mu_1 ... mu_step (1 at step 0), in double."""
+        key = (float(beta1), float(momentum_decay))
+        if key != self._mv_mu_key:
+            self._mv_mu_key, self._mv_mu_products = key, [1.0]
+        ps = self._mv_mu_products
+        while len(ps) <= step:
+            ps.append(ps[-1] * K.nadam_mu(len(ps), *key))
+        return ps[step]
+
+    def _mv_coefficients(self, a):
+        """(cg, cm, bc2) of the step the arena's counter stands at."""
+        hp = a.group
+        b1, b2 = (float(b) for b in hp["betas"])
+        md = float(hp["momentum_decay"])
+        cg, cm = K.nadam_coefficients(K.nadam_mu(a.step, b1, md), K.nadam_mu(a.step + 1, b1, md),
+                                      self.mu_product(a.step, b1, md))
+        return cg, cm, 1.0 - b2 ** a.step
+
+    def _mv_dyn_values(self, a):
+        cg, cm, bc2 = self._mv_coefficients(a)
+        return [float(a.group["lr"]), cg, cm, bc2]
+
+    def state_dict(self):
+        for a in self._mv_arenas or []:
+            p_t = self.mu_product(a.step, float(a.group["betas"][0]),
+                                  float(a.group["momentum_decay"]))
+            for p in a.params:
+                self.state[p]["mu_product"] = torch.tensor(p_t)
+        return super().state_dict()
+
+    def _mv_apply(self, a, i0, i1, gscale=1.0):
+        g, w, st, model = self._mv_slices(a, i0, i1)
+        hp = a.group
+        b1, b2 = hp["betas"]
+        cg, cm, bc2 = self._mv_coefficients(a)
+        K.nadam_step(g, w, st["exp_avg"], st["exp_avg_sq"], model, lr=hp["lr"], cg=cg, cm=cm,
+                     bc2=bc2, beta1=b1, beta2=b2, eps=hp["eps"], weight_decay=hp["weight_decay"],
+                     gscale=gscale, adamw=hp["decoupled_weight_decay"], dyn=self._mv_dyn(a),
+                     skip=self._mv_skip, gclip=self._mv_clip)

@@ -14,7 +14,9 @@ What makes a replay equal to an eager step:
 * **Device-side hyperparameters.**  While the step is captured the fused
   optimizer kernels are launched with a 16-byte device block per arena,
   ``[lr, first, bias_correction1, bias_correction2]`` (``dyn`` in
-  csrc/kernels/mv_kernels.hip), instead of baked launch arguments.  Before
+  csrc/kernels/mv_kernels.hip), instead of baked launch arguments.  The
+  optimizer supplies the four values (``FusedOptimizer._mv_dyn_values``):
+  ``FusedNAdam``'s block is ``[lr, cg, cm, bias_correction2]``.  Before
   every replay the host refills it from the param groups — so LR warmup and
   schedules keep working — through a ring of pinned staging buffers (async
   H2D; a slot is reused only after its copy has completed).
@@ -52,7 +54,7 @@ from typing import Callable, List, Optional
 
 import torch
 
-from ..optim.fused import FusedOptimizer
+from ..optim.fused import FusedOptimizer, dyn_values  # noqa: F401  (dyn_values: the default block)
 
 
 class _DynRing:
@@ -76,17 +78,6 @@ class _DynRing:
         ev = torch.cuda.Event()
         ev.record()
         self.events[k] = ev
-
-
-def dyn_values(a) -> List[float]:
-    """[lr, first, bc1, bc2] of arena ``a`` for its current ``a.step``."""
-    g = a.group
-    bc1 = bc2 = 1.0
-    betas = g.get("betas")
-    if betas is not None:
-        bc1 = 1.0 - float(betas[0]) ** a.step
-        bc2 = 1.0 - float(betas[1]) ** a.step
-    return [float(g["lr"]), 1.0 if a.step == 1 else 0.0, bc1, bc2]
 
 
 class GraphedStep:
@@ -182,7 +173,7 @@ class GraphedStep:
         for a in self.arenas:
             a.sync_master_if_modified()      # params edited in place since the last step
             a.step += 1
-            vals.extend(dyn_values(a))
+            vals.extend(self.opt._mv_dyn_values(a))
         host.copy_(torch.tensor(vals, dtype=torch.float32))
         for i, a in enumerate(self.arenas):
             a.dyn.copy_(host[4 * i:4 * i + 4], non_blocking=True)
