@@ -7,6 +7,7 @@ with fp16 gradient compression + Adasum through mivod.torch.DistributedOptimizer
     python benchmarks/bench_bert.py --max-grad-norm 1.0   # with global gradient-norm clipping
     python benchmarks/bench_bert.py --backward-passes 4 --accumulation-dtype fp32
                                                           # 4 micro-batches per step, summed in fp32
+    python benchmarks/bench_bert.py --ema-decay 0.999     # with the fp32 weight average
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
         benchmarks/bench_bert.py --gpus 8
 Prints one JSON line (sequences/sec for the whole job) with a ``comm`` record.
@@ -68,6 +69,9 @@ def main():
                          "(backward_passes_per_step); default 1")
     ap.add_argument("--accumulation-dtype", default="none", choices=["none", "fp32"],
                     help="none: the passes accumulate in p.grad (bf16); fp32: in the fp32 arena")
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="keep an fp32 moving average of the weights (FusedAdam's ema_decay); "
+                         "default off")
     args = ap.parse_args()
     if args.gpus > 1 and not any(k in os.environ for k in ("WORLD_SIZE", "HOROVOD_RANK")):
         sys.path.insert(0, ROOT)
@@ -96,7 +100,7 @@ def main():
     torch.manual_seed(7)
     model = BertForPreTraining(cfg).to(dev).to(torch.bfloat16)
     opt = FusedAdam(model.parameters(), lr=args.lr, weight_decay=0.01, adamw=True,
-                    max_grad_norm=args.max_grad_norm)
+                    max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay)
     op = hvd.Adasum if args.op == "adasum" else hvd.Average
     opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(),
                                    compression=hvd.Compression.by_name(args.compression), op=op,
@@ -176,6 +180,7 @@ def main():
                        "optimizer": "mivod FusedAdamW", "max_grad_norm": args.max_grad_norm,
                        "backward_passes_per_step": passes,
                        "accumulation_dtype": args.accumulation_dtype,
+                       "ema_decay": args.ema_decay,
                        "transport": basics.state().backend if size > 1 else "local"},
             "comm": comm}), flush=True)
     hvd.shutdown()

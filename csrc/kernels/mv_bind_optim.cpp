@@ -1,11 +1,12 @@
 // mivod._mvk bindings: multi-tensor pack / cast, fused optimizer steps, global gradient-norm
-// clipping, local gradient accumulation, Adasum (mv_kernels.h, mv_adaptive.h, mv_adamfam.h,
-// mv_clip.h, mv_accum.h)
+// clipping, local gradient accumulation, weight averaging, Adasum (mv_kernels.h, mv_adaptive.h,
+// mv_adamfam.h, mv_clip.h, mv_accum.h, mv_ema.h)
 #include "mv_accum.h"
 #include "mv_adamfam.h"
 #include "mv_adaptive.h"
 #include "mv_checks.h"
 #include "mv_clip.h"
+#include "mv_ema.h"
 #include "mv_kernels.h"
 
 #include <algorithm>
@@ -497,6 +498,54 @@ void clip_finalize(at::Tensor partial, int64_t total, double gscale, double max_
   mv_launch_clip_finalize(pp, total, gscale, max_norm, cp, cur_stream());
 }
 
+// Weight averaging (mv_ema.hip) over the flat fp32 ranges w (master) and e (average) of equal
+// length, at any offset; model is the optional low-precision copy of w.
+struct EmaArgs {
+  float* w;
+  float* e;
+  void* model = nullptr;
+  int model_dt = 0;
+  const int* skip;
+};
+
+EmaArgs ema_args(const char* fn, const at::Tensor& w, const at::Tensor& e, const OptTensor& model,
+                 const OptTensor& skip) {
+  EmaArgs s;
+  s.w = vec_ptr(fn, "master", w, w, w.numel());
+  s.e = vec_ptr(fn, "ema", e, w, w.numel());
+  if (given(model)) {
+    check_dense(fn, "model", *model, w);
+    TORCH_CHECK(model->numel() == w.numel(), fn, ": model must hold exactly ", w.numel(),
+                " elements, not ", model->numel());
+    s.model = model->data_ptr();
+    s.model_dt = dtype_code(*model);
+  }
+  s.skip = flag_ptr(fn, "skip", skip, w);
+  return s;
+}
+
+void ema_update(at::Tensor w, at::Tensor e, double decay, c10::optional<at::Tensor> skip) {
+  const EmaArgs s = ema_args("ema_update", w, e, c10::nullopt, skip);
+  TORCH_CHECK(decay >= 0.0 && decay < 1.0, "ema_update: decay must be in [0, 1), not ", decay);
+  c10::DeviceGuard guard(w.device());
+  // 1 - decay in double, rounded to fp32 once
+  mv_launch_ema_update(s.w, s.e, w.numel(), (float)(1.0 - decay), s.skip, cur_stream());
+}
+
+void ema_swap(at::Tensor w, at::Tensor e, c10::optional<at::Tensor> model,
+              c10::optional<at::Tensor> skip) {
+  const EmaArgs s = ema_args("ema_swap", w, e, model, skip);
+  c10::DeviceGuard guard(w.device());
+  mv_launch_ema_swap(s.w, s.e, s.model, s.model_dt, w.numel(), s.skip, cur_stream());
+}
+
+void ema_overwrite(at::Tensor w, at::Tensor e, c10::optional<at::Tensor> model,
+                   c10::optional<at::Tensor> skip) {
+  const EmaArgs s = ema_args("ema_overwrite", w, e, model, skip);
+  c10::DeviceGuard guard(w.device());
+  mv_launch_ema_overwrite(s.w, s.e, s.model, s.model_dt, w.numel(), s.skip, cur_stream());
+}
+
 void seg_dot3(at::Tensor a, at::Tensor b, at::Tensor cbeg, at::Tensor clen, at::Tensor cseg,
               at::Tensor seg_c0, at::Tensor seg_nc, at::Tensor partial, at::Tensor out,
               bool swap) {
@@ -618,6 +667,13 @@ void bind_optim(pybind11::module_& m) {
          "acc[off_i : off_i + n_i] = float(t_i) (first) or += float(t_i), one launch");
   ac.def("pack_accumulated", &pack_accumulated,
          "dst[off_i : off_i + n_i] = cast((acc[off_i : off_i + n_i] + float(t_i)) * scale)");
+  // and the fp32 moving average of the master weights: mivod._mvk._ema
+  pybind11::module_ em = m.def_submodule(
+      "_ema", "fp32 exponential moving average of the master weights (ema_decay)");
+  em.def("ema_update", &ema_update,
+         "e = e + fp32(1 - decay) * (w - e); e = w where fp32(1 - decay) == 1");
+  em.def("ema_swap", &ema_swap, "(w, e) = (e, w); model = cast(new w)");
+  em.def("ema_overwrite", &ema_overwrite, "w = e; model = cast(e)");
   m.def("seg_dot3", &seg_dot3, "per-segment (a.b, |a|^2, |b|^2) (swap: (a.b, |b|^2, |a|^2))");
   m.def("adasum_merge", &adasum_merge,
         "one vector-halving Adasum level: merge with fixed-order group Gram sums + fused wire cast");

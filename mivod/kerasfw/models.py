@@ -287,6 +287,11 @@ class Model(nn.Module):
             cb.on_epoch_end(epoch, epoch_logs)
             if self.stop_training:
                 break
+        # tf.keras: with use_ema and no overwrite frequency the variables take their moving
+        # average when training ends
+        if getattr(self.optimizer, "use_ema", False) and \
+                not self.optimizer.ema_overwrite_frequency:
+            self.optimizer.finalize_variable_values(self.trainable_weights)
         cb.on_train_end({})
         return self.history
 
@@ -515,4 +520,6 @@ def load_model(filepath, custom_objects=None, compile=True):
             if hasattr(opt._impl, "_mv_arenas"):
                 for a in opt._impl._mv_arenas or []:
                     a.step = opt.iterations
+                if opt.use_ema:                  # the saved average, not one seeded anew
+                    opt._impl._mv_adopt_ema(opt.iterations)
     return model

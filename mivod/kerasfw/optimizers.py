@@ -13,6 +13,11 @@ FusedAdamax with Keras epsilon placement / FusedNAdam): one launch
 per arena on the GPU, the plain-PyTorch reference math on the CPU.  RMSprop and
 Adagrad keep torch's form (epsilon outside the root; RMSprop's rate outside its
 momentum buffer): see their docstrings for what that changes against tf.keras.
+
+``use_ema`` / ``ema_momentum`` / ``ema_overwrite_frequency`` (tf.keras's names, taken by
+every optimizer) keep an fp32 exponential moving average of the trainable variables on the
+fused path (``ema_decay`` of the Fused* optimizers, docs/EMA.md).  As in Keras only the
+variables the optimizer updates are averaged: BatchNorm's moving mean and variance are not.
 """
 from __future__ import annotations
 
@@ -36,6 +41,16 @@ class Optimizer:
         self.decay = float(kwargs.pop("decay", 0.0))
         self.clipnorm = kwargs.pop("clipnorm", None)
         self.clipvalue = kwargs.pop("clipvalue", None)
+        self.use_ema = bool(kwargs.pop("use_ema", False))
+        self.ema_momentum = float(kwargs.pop("ema_momentum", 0.99))
+        self.ema_overwrite_frequency = kwargs.pop("ema_overwrite_frequency", None)
+        if self.use_ema:
+            if not 0.0 <= self.ema_momentum < 1.0:
+                raise ValueError(f"ema_momentum must be in [0, 1), not {self.ema_momentum}")
+            f = self.ema_overwrite_frequency
+            if f is not None and (not isinstance(f, int) or f < 1):
+                raise ValueError("ema_overwrite_frequency must be an integer >= 1 or None, "
+                                 f"not {f!r}")
         self._name = name or type(self).__name__
         self.iterations = 0
         self._impl = None
@@ -62,6 +77,11 @@ class Optimizer:
     def _make_impl(self, params):
         raise NotImplementedError
 
+    @property
+    def _ema_decay(self):
+        """``ema_decay`` of the fused optimizer: ``ema_momentum`` with ``use_ema``, else None."""
+        return self.ema_momentum if self.use_ema else None
+
     def _sync_hyper(self):
         lr = float(self.lr)
         if self.decay:
@@ -85,6 +105,16 @@ class Optimizer:
         for p in params:
             p.grad = None
         self.iterations += 1
+        if self.use_ema and self.ema_overwrite_frequency and \
+                self.iterations % self.ema_overwrite_frequency == 0:
+            self._impl.ema_overwrite()
+
+    def finalize_variable_values(self, var_list=None):
+        """With ``use_ema``: the variables take their moving average (tf.keras calls this at
+        the end of ``fit`` when no ``ema_overwrite_frequency`` is given).  Every variable the
+        optimizer updates is overwritten; ``var_list`` is accepted for parity."""
+        if self.use_ema and self._impl is not None:
+            self._impl.ema_overwrite()
 
     def minimize(self, loss, var_list):
         self.apply_gradients(zip(self.get_gradients(loss, var_list), var_list))
@@ -95,6 +125,9 @@ class Optimizer:
         for h in self._hyper:
             v = getattr(self, h)
             cfg[h] = float(v) if isinstance(v, Variable) else v
+        if self.use_ema:
+            cfg.update(use_ema=True, ema_momentum=self.ema_momentum,
+                       ema_overwrite_frequency=self.ema_overwrite_frequency)
         return cfg
 
     @classmethod
@@ -149,7 +182,7 @@ class SGD(Optimizer):
     def _make_impl(self, params):
         from ..optim import FusedSGD
         return FusedSGD(params, lr=float(self.lr), momentum=float(self.momentum) or 0.0,
-                        nesterov=self.nesterov)
+                        nesterov=self.nesterov, ema_decay=self._ema_decay)
 
     def _sync_hyper(self):
         super()._sync_hyper()
@@ -170,7 +203,8 @@ class Adam(Optimizer):
     def _make_impl(self, params):
         from ..optim import FusedAdam
         return FusedAdam(params, lr=float(self.lr), betas=(self.beta_1, self.beta_2),
-                         eps=self.epsilon, keras_eps=True, amsgrad=self.amsgrad)
+                         eps=self.epsilon, keras_eps=True, amsgrad=self.amsgrad,
+                         ema_decay=self._ema_decay)
 
 
 class Adamax(Optimizer):
@@ -189,7 +223,7 @@ class Adamax(Optimizer):
     def _make_impl(self, params):
         from ..optim import FusedAdamax
         return FusedAdamax(params, lr=float(self.lr), betas=(self.beta_1, self.beta_2),
-                           eps=self.epsilon, keras_eps=True)
+                           eps=self.epsilon, keras_eps=True, ema_decay=self._ema_decay)
 
 
 class Nadam(Optimizer):
@@ -209,7 +243,8 @@ class Nadam(Optimizer):
     def _make_impl(self, params):
         from ..optim import FusedNAdam
         return FusedNAdam(params, lr=float(self.lr), betas=(self.beta_1, self.beta_2),
-                          eps=self.epsilon, momentum_decay=self.schedule_decay)
+                          eps=self.epsilon, momentum_decay=self.schedule_decay,
+                          ema_decay=self._ema_decay)
 
 
 class Adadelta(Optimizer):
@@ -224,7 +259,8 @@ class Adadelta(Optimizer):
 
     def _make_impl(self, params):
         from ..optim import FusedAdadelta
-        return FusedAdadelta(params, lr=float(self.lr), rho=self.rho, eps=self.epsilon)
+        return FusedAdadelta(params, lr=float(self.lr), rho=self.rho, eps=self.epsilon,
+                             ema_decay=self._ema_decay)
 
 
 def epsilon_default():
@@ -255,7 +291,8 @@ class RMSprop(Optimizer):
     def _make_impl(self, params):
         from ..optim import FusedRMSprop
         return FusedRMSprop(params, lr=float(self.lr), alpha=self.rho, eps=self.epsilon,
-                            momentum=float(self.momentum) or 0.0, centered=self.centered)
+                            momentum=float(self.momentum) or 0.0, centered=self.centered,
+                            ema_decay=self._ema_decay)
 
 
 class Adagrad(Optimizer):
@@ -274,7 +311,8 @@ class Adagrad(Optimizer):
     def _make_impl(self, params):
         from ..optim import FusedAdagrad
         return FusedAdagrad(params, lr=float(self.lr), eps=self.epsilon,
-                            initial_accumulator_value=self.initial_accumulator_value)
+                            initial_accumulator_value=self.initial_accumulator_value,
+                            ema_decay=self._ema_decay)
 
 
 OPTIMIZERS = {"SGD": SGD, "Adam": Adam, "Adadelta": Adadelta, "RMSprop": RMSprop,

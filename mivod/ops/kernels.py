@@ -178,6 +178,76 @@ def pack_accumulated(tensors: Sequence[torch.Tensor], acc: torch.Tensor, dst: to
 
 
 # ---------------------------------------------------------------------------
+# fp32 exponential moving average of the master weights (ema_decay of the Fused* optimizers)
+# ---------------------------------------------------------------------------
+def ema_omd(decay: float) -> float:
+    """1 - decay taken in float64 and rounded once to fp32: the factor of ``ema_update``."""
+    decay = float(decay)
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"ema_update: decay must be in [0, 1), not {decay}")
+    return float(torch.tensor(1.0 - decay, dtype=torch.float64).to(torch.float32))
+
+
+def _check_ema(fn, w, e, model=None) -> None:
+    for what, t in (("master", w), ("ema", e)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{fn}: {what} must be a contiguous fp32 tensor")
+    if e.numel() != w.numel() or (model is not None and model.numel() != w.numel()):
+        raise ValueError(f"{fn}: every stream must hold exactly {w.numel()} elements")
+
+
+def ema_update(w: torch.Tensor, e: torch.Tensor, *, decay: float,
+               skip: Optional[torch.Tensor] = None) -> None:
+    """e = e + omd * (w - e) over two flat fp32 ranges of equal length, omd = fp32(1 - decay):
+    a difference, a product and a sum, each rounded to fp32.  Where omd == 1 (decay 0) ``e``
+    receives ``w`` itself, the copying first update.  ``w`` is only read.  ``skip``: device
+    int32 flag; nonzero => nothing is stored (the overflow guard's)."""
+    omd = ema_omd(decay)
+    if _on_gpu(w):
+        native()._ema.ema_update(w, e, float(decay), skip)
+        return
+    _check_ema("ema_update", w, e)
+    if _skipped(skip):
+        return
+    if omd == 1.0:
+        e.copy_(w)
+        return
+    d = w - e
+    d.mul_(omd)
+    e.add_(d)
+
+
+def ema_swap(w: torch.Tensor, e: torch.Tensor, model: Optional[torch.Tensor], *,
+             skip: Optional[torch.Tensor] = None) -> None:
+    """(w, e) = (e, w) exactly, and model = cast(new w) where a model copy is given."""
+    if _on_gpu(w):
+        native()._ema.ema_swap(w, e, model, skip)
+        return
+    _check_ema("ema_swap", w, e, model)
+    if _skipped(skip):
+        return
+    t = w.clone()
+    w.copy_(e)
+    e.copy_(t)
+    if model is not None:
+        model.copy_(w)
+
+
+def ema_overwrite(w: torch.Tensor, e: torch.Tensor, model: Optional[torch.Tensor], *,
+                  skip: Optional[torch.Tensor] = None) -> None:
+    """w = e and model = cast(e); ``e`` is only read."""
+    if _on_gpu(w):
+        native()._ema.ema_overwrite(w, e, model, skip)
+        return
+    _check_ema("ema_overwrite", w, e, model)
+    if _skipped(skip):
+        return
+    w.copy_(e)
+    if model is not None:
+        model.copy_(e)
+
+
+# ---------------------------------------------------------------------------
 # Global gradient-norm clipping (max_grad_norm of the Fused* optimizers)
 # ---------------------------------------------------------------------------
 def sumsq_chunks(n: int) -> int:

@@ -18,6 +18,7 @@ and LARS (large-batch ResNet), per BASELINE.json north star.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict, List, Optional
 
@@ -40,6 +41,17 @@ def check_max_grad_norm(v):
     f = float(v)
     if not (math.isfinite(f) and f > 0.0):
         raise ValueError(f"max_grad_norm must be a positive finite number or None, not {v!r}")
+    return f
+
+
+def check_ema_decay(v):
+    """``ema_decay`` as a float, or None when weight averaging is off; a value outside
+    [0, 1) raises."""
+    if v is None:
+        return None
+    f = float(v)
+    if not 0.0 <= f < 1.0:
+        raise ValueError(f"ema_decay must be in [0, 1) or None, not {v!r}")
     return f
 
 
@@ -106,6 +118,9 @@ class Arena:
         self.tables: Dict[tuple, K.ChunkTable] = {}
         self.workspace: Dict[str, torch.Tensor] = {}
         self.dyn: Optional[torch.Tensor] = None   # [lr, first, bc1, bc2] for graph replays
+        self.ema: Optional[torch.Tensor] = None   # fp32 average of the master (ema_decay)
+        self.ema_updates = 0                      # updates counted, the copying first included
+        self.ema_counted = False                  # the current step advanced ema_updates
 
     # -- views ---------------------------------------------------------------
     def slot(self, flat: torch.Tensor, i: int) -> torch.Tensor:
@@ -156,12 +171,25 @@ class FusedOptimizer(torch.optim.Optimizer):
     ``mivod.torch.DistributedOptimizer`` the norm is that of the reduced (averaged) gradient
     with no extra collective.  It is a plain attribute, not part of ``param_groups`` or
     ``state_dict()``, and may be changed or set to None between eager steps; a HIP graph
-    keeps the value it was captured with.  ``grad_norm()`` reads the last measured norm."""
+    keeps the value it was captured with.  ``grad_norm()`` reads the last measured norm.
+
+    ``ema_decay`` (every ``Fused*`` constructor takes it; default None = off) keeps an fp32
+    exponential moving average of the fp32 master weights in one more flat arena, 4 bytes per
+    parameter, allocated and seeded with the weights at the start of the first step that runs
+    with it on: after every update, one streaming pass (csrc/kernels/mv_ema.hip) behind the
+    fused step, on the same stream and under the same overflow-guard flag, computes
+    ema += (1 - ema_decay) * (w - ema); the first update copies the weights
+    (``torch.optim.swa_utils.AveragedModel`` and Keras 3 start there too).  Like
+    ``max_grad_norm`` it is a plain attribute that may be changed or set to None between
+    eager steps, and a HIP graph keeps the value it was captured with.
+    ``ema_parameters()`` evaluates with the average, ``ema_overwrite()`` adopts it, and
+    ``state_dict()`` carries it as ``ema_param`` / ``ema_updates`` while it exists.  See
+    docs/EMA.md."""
 
     _state_names: List[str] = []
 
     def __init__(self, params, defaults, grad_dtype: Optional[torch.dtype] = None,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None):
         super().__init__(params, defaults)
         self._mv_arenas: Optional[List[Arena]] = None
         self._mv_grad_dtype = grad_dtype
@@ -173,6 +201,8 @@ class FusedOptimizer(torch.optim.Optimizer):
         self._mv_clip_ws = None           # fp32 sum-of-squares partials, one per 4096 elements
         check_max_grad_norm(max_grad_norm)
         self.max_grad_norm = max_grad_norm
+        check_ema_decay(ema_decay)
+        self.ema_decay = ema_decay
 
     # ---- layout ----------------------------------------------------------
     def _mv_build(self, grad_dtype_for=None) -> List[Arena]:
@@ -203,12 +233,28 @@ class FusedOptimizer(torch.optim.Optimizer):
                     st[n] = a.slot(flat, i)
                 if a.low_precision:
                     st["master_param"] = a.slot(a.master, i)
+                if a.ema is not None:
+                    st["ema_param"] = a.slot(a.ema, i)
+                    st["ema_updates"] = torch.tensor(float(a.ema_updates))
                 st["step"] = torch.tensor(float(a.step))
 
     def _mv_begin_step(self):
+        decay = check_ema_decay(self.ema_decay)
         for a in self._mv_build():
             a.sync_master_if_modified()
             a.step += 1
+            a.ema_counted = decay is not None
+            if a.ema_counted:
+                self._mv_ema_arena(a)
+                a.ema_updates += 1
+
+    def _mv_uncount_step(self, a: Arena):
+        """The step that ``_mv_begin_step`` counted last took no update of ``a`` (the overflow
+        guard skipped it): neither the step nor its EMA update is counted."""
+        a.step = max(a.step - 1, 0)
+        if a.ema_counted:
+            a.ema_updates = max(a.ema_updates - 1, 0)
+            a.ema_counted = False
 
     def _mv_end_step(self):
         for a in self._mv_arenas or []:
@@ -218,7 +264,88 @@ class FusedOptimizer(torch.optim.Optimizer):
         for a in self._mv_arenas or []:
             for p in a.params:
                 self.state[p]["step"] = torch.tensor(float(a.step))
+                if a.ema is not None:
+                    self.state[p]["ema_updates"] = torch.tensor(float(a.ema_updates))
         return super().state_dict()
+
+    # ---- the fp32 moving average of the master weights ----------------------
+    def _mv_ema_arena(self, a: Arena) -> torch.Tensor:
+        """The arena's fp32 EMA, allocated on first use and seeded with the master."""
+        if a.ema is None:
+            if self._mv_graph:
+                raise RuntimeError("ema_decay must be set before make_graphed_step's eager "
+                                   "warmup: a HIP-graph capture cannot allocate the EMA arena")
+            a.ema = a.master.clone()
+            a.ema_updates = 0
+            self._mv_expose_state()
+        return a.ema
+
+    def _mv_apply_ema(self, a: Arena, i0: int, i1: int):
+        """The EMA update of params [i0, i1) of ``a``, right behind their fused step: same
+        stream, same skip flag.  The arena's first counted update copies the weights."""
+        decay = check_ema_decay(self.ema_decay)
+        if decay is None or not a.ema_counted:
+            return
+        if a.ema_updates <= 1:
+            if self._mv_graph:
+                raise RuntimeError("a HIP-graph capture needs an eager step with ema_decay set "
+                                   "before it (the copying first EMA update)")
+            decay = 0.0
+        lo, hi = a.range_of(i0, i1)
+        K.ema_update(a.master[lo:hi], a.ema[lo:hi], decay=decay, skip=self._mv_skip)
+
+    def _mv_ema_sync(self):
+        """Hook of DistributedOptimizer: refuse inside a step, order after the comm stream."""
+
+    @contextlib.contextmanager
+    def ema_parameters(self):
+        """Context manager: inside it the parameters (fp32 master, low-precision model copy
+        and therefore every parameter view) hold the moving average; on exit the training
+        weights are back bit for bit (the exchange is exact).  Do not step inside it."""
+        arenas = [a for a in self._mv_build() if a.ema is not None]
+        if not arenas:
+            raise RuntimeError("ema_parameters(): no step has run with ema_decay set")
+        self._mv_ema_sync()
+        for a in self._mv_arenas:
+            a.sync_master_if_modified()
+        self._mv_ema_exchange(arenas)
+        try:
+            yield self
+        finally:
+            self._mv_ema_sync()
+            self._mv_ema_exchange(arenas)
+
+    @torch.no_grad()
+    def _mv_ema_exchange(self, arenas):
+        for a in arenas:
+            K.ema_swap(a.master, a.ema, a.model if a.low_precision else None)
+            a.versions = [p._version for p in a.params]
+
+    @torch.no_grad()
+    def ema_overwrite(self):
+        """Adopt the moving average as the training weights: master = ema, model copy =
+        cast(ema).  The average itself is untouched."""
+        arenas = [a for a in self._mv_build() if a.ema is not None]
+        if not arenas:
+            raise RuntimeError("ema_overwrite(): no step has run with ema_decay set")
+        self._mv_ema_sync()
+        for a in arenas:
+            a.sync_master_if_modified()
+            K.ema_overwrite(a.master, a.ema, a.model if a.low_precision else None)
+            a.versions = [p._version for p in a.params]
+
+    @torch.no_grad()
+    def _mv_adopt_ema(self, updates: int):
+        """Per-parameter ``ema_param`` entries that a loader other than ``load_state_dict``
+        put into ``self.state`` (mivod.kerasfw.load_model) become the arenas' average."""
+        for a in self._mv_build():
+            saved = [self.state[p].get("ema_param") for p in a.params]
+            if a.ema is None and all(torch.is_tensor(t) for t in saved):
+                a.ema = a.master.clone()
+                for i, t in enumerate(saved):
+                    a.slot(a.ema, i).copy_(t)
+                a.ema_updates = int(updates)
+        self._mv_expose_state()
 
     # ---- the fused update of a bucket ------------------------------------
     def _mv_apply(self, a: Arena, i0: int, i1: int, gscale: float = 1.0):
@@ -302,6 +429,7 @@ class FusedOptimizer(torch.optim.Optimizer):
                 if not self._mv_external_grads:
                     self._mv_pack_local(a)
                 self._mv_apply(a, 0, len(a.params), 1.0)
+                self._mv_apply_ema(a, 0, len(a.params))
         elif arenas:
             # every arena packed and measured before the first update: the coefficient is
             # global.  The alignment gaps of an arena are zeros, so its whole range is summed.
@@ -319,6 +447,7 @@ class FusedOptimizer(torch.optim.Optimizer):
             try:
                 for a in arenas:
                     self._mv_apply(a, 0, len(a.params), 1.0)
+                    self._mv_apply_ema(a, 0, len(a.params))
             finally:
                 self._mv_clip = None
         self._mv_end_step()
@@ -343,9 +472,11 @@ class FusedOptimizer(torch.optim.Optimizer):
         # torch replaced our views with fresh tensors: copy them back into the arenas
         with torch.no_grad():
             for a in arenas:
-                steps = []
+                steps, emas = [], []
                 for i, p in enumerate(a.params):
                     st = raw.get(p) or self.state.get(p, {})
+                    if "ema_param" in st and "ema_updates" in st:
+                        emas.append((i, st["ema_param"], float(st["ema_updates"])))
                     for n, flat in a.state.items():
                         if n in st and torch.is_tensor(st[n]):
                             a.slot(flat, i).copy_(st[n])
@@ -359,6 +490,23 @@ class FusedOptimizer(torch.optim.Optimizer):
                 if steps:
                     a.step = int(max(steps))
                 a.versions = [p._version for p in a.params]
+                if len(emas) == len(a.params):
+                    # the exact fp32 average, as master_param above
+                    if a.ema is None:
+                        a.ema = a.master.clone()
+                    for i, e, _ in emas:
+                        a.slot(a.ema, i).copy_(e)
+                    a.ema_updates = int(max(n for _, _, n in emas))
+                else:
+                    # a dict without the average: the next step with ema_decay set seeds a
+                    # new one from the weights it finds
+                    a.ema = None
+                    a.ema_updates = 0
+                a.ema_counted = False
+        # entries torch copied from a dict that this optimizer does not keep
+        for st in self.state.values():
+            st.pop("ema_param", None)
+            st.pop("ema_updates", None)
         self._mv_expose_state()
 
     def zero_grad(self, set_to_none: bool = True):
@@ -370,13 +518,13 @@ class FusedSGD(FusedOptimizer):
     semantics, momentum buffer seeded with the first gradient)."""
 
     def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0,
-                 nesterov=False, grad_dtype=None, max_grad_norm=None):
+                 nesterov=False, grad_dtype=None, max_grad_norm=None, ema_decay=None):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         self._state_names = ["momentum_buffer"] if momentum != 0 else []
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening,
                                       weight_decay=weight_decay, nesterov=nesterov), grad_dtype,
-                         max_grad_norm)
+                         max_grad_norm, ema_decay)
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
         g, w, st, model = self._mv_slices(a, i0, i1)
@@ -401,14 +549,15 @@ class FusedAdam(FusedOptimizer):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  adamw=False, keras_eps=False, grad_dtype=None, max_grad_norm=None,
-                 amsgrad=False):
+                 amsgrad=False, ema_decay=None):
         _check_adam_ranges(type(self).__name__, lr, betas, eps, weight_decay)
         self._mv_amsgrad = bool(amsgrad)
         if self._mv_amsgrad:
             self._state_names = ["exp_avg", "exp_avg_sq", "max_exp_avg_sq"]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       adamw=adamw, keras_eps=keras_eps,
-                                      amsgrad=self._mv_amsgrad), grad_dtype, max_grad_norm)
+                                      amsgrad=self._mv_amsgrad),
+                         grad_dtype, max_grad_norm, ema_decay)
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
         g, w, st, model = self._mv_slices(a, i0, i1)
@@ -426,9 +575,9 @@ class FusedAdam(FusedOptimizer):
 
 class FusedAdamW(FusedAdam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 grad_dtype=None, max_grad_norm=None, amsgrad=False):
+                 grad_dtype=None, max_grad_norm=None, amsgrad=False, ema_decay=None):
         super().__init__(params, lr, betas, eps, weight_decay, adamw=True, grad_dtype=grad_dtype,
-                         max_grad_norm=max_grad_norm, amsgrad=amsgrad)
+                         max_grad_norm=max_grad_norm, amsgrad=amsgrad, ema_decay=ema_decay)
 
 
 class FusedAdadelta(FusedOptimizer):
@@ -437,9 +586,9 @@ class FusedAdadelta(FusedOptimizer):
     _state_names = ["square_avg", "acc_delta"]
 
     def __init__(self, params, lr=1.0, rho=0.9, eps=1e-6, weight_decay=0.0, grad_dtype=None,
-                 max_grad_norm=None):
+                 max_grad_norm=None, ema_decay=None):
         super().__init__(params, dict(lr=lr, rho=rho, eps=eps, weight_decay=weight_decay),
-                         grad_dtype, max_grad_norm)
+                         grad_dtype, max_grad_norm, ema_decay)
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
         g, w, st, model = self._mv_slices(a, i0, i1)
@@ -457,9 +606,10 @@ class FusedLARS(FusedOptimizer):
     _state_names = ["momentum_buffer"]
 
     def __init__(self, params, lr=0.1, momentum=0.9, weight_decay=1e-4, eta=0.001, eps=0.0,
-                 exclude_1d=True, grad_dtype=None, max_grad_norm=None):
+                 exclude_1d=True, grad_dtype=None, max_grad_norm=None, ema_decay=None):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, eta=eta,
-                                      eps=eps, exclude_1d=exclude_1d), grad_dtype, max_grad_norm)
+                                      eps=eps, exclude_1d=exclude_1d),
+                         grad_dtype, max_grad_norm, ema_decay)
         self._mv_flags: Dict[tuple, torch.Tensor] = {}
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
@@ -494,9 +644,9 @@ class FusedLAMB(FusedOptimizer):
     _state_names = ["exp_avg", "exp_avg_sq"]
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01,
-                 exclude_1d=True, grad_dtype=None, max_grad_norm=None):
+                 exclude_1d=True, grad_dtype=None, max_grad_norm=None, ema_decay=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      exclude_1d=exclude_1d), grad_dtype, max_grad_norm)
+                                      exclude_1d=exclude_1d), grad_dtype, max_grad_norm, ema_decay)
         self._mv_flags: Dict[tuple, torch.Tensor] = {}
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
@@ -525,14 +675,14 @@ class FusedRMSprop(FusedOptimizer):
     non-zero values."""
 
     def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0,
-                 centered=False, grad_dtype=None, max_grad_norm=None):
+                 centered=False, grad_dtype=None, max_grad_norm=None, ema_decay=None):
         if lr < 0 or eps < 0 or alpha < 0 or momentum < 0 or weight_decay < 0:
             raise ValueError("FusedRMSprop: lr, alpha, eps, momentum and weight_decay must be >= 0")
         self._state_names = (["square_avg"] + (["momentum_buffer"] if momentum != 0 else [])
                              + (["grad_avg"] if centered else []))
         super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay,
                                       momentum=momentum, centered=bool(centered)), grad_dtype,
-                         max_grad_norm)
+                         max_grad_norm, ema_decay)
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
         g, w, st, model = self._mv_slices(a, i0, i1)
@@ -553,13 +703,13 @@ class FusedAdagrad(FusedOptimizer):
     _state_names = ["sum"]
 
     def __init__(self, params, lr=1e-2, lr_decay=0, weight_decay=0, initial_accumulator_value=0,
-                 eps=1e-10, grad_dtype=None, max_grad_norm=None):
+                 eps=1e-10, grad_dtype=None, max_grad_norm=None, ema_decay=None):
         if lr < 0 or lr_decay < 0 or weight_decay < 0 or initial_accumulator_value < 0 or eps < 0:
             raise ValueError("FusedAdagrad: lr, lr_decay, weight_decay, "
                              "initial_accumulator_value and eps must be >= 0")
         super().__init__(params, dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay,
                                       initial_accumulator_value=initial_accumulator_value),
-                         grad_dtype, max_grad_norm)
+                         grad_dtype, max_grad_norm, ema_decay)
 
     def _mv_build(self, grad_dtype_for=None):
         if self._mv_arenas is None:
@@ -594,10 +744,11 @@ class FusedAdamax(FusedOptimizer):
     _state_names = ["exp_avg", "exp_inf"]
 
     def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 keras_eps=False, grad_dtype=None, max_grad_norm=None):
+                 keras_eps=False, grad_dtype=None, max_grad_norm=None, ema_decay=None):
         _check_adam_ranges("FusedAdamax", lr, betas, eps, weight_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      keras_eps=bool(keras_eps)), grad_dtype, max_grad_norm)
+                                      keras_eps=bool(keras_eps)),
+                         grad_dtype, max_grad_norm, ema_decay)
 
     def _mv_apply(self, a, i0, i1, gscale=1.0):
         g, w, st, model = self._mv_slices(a, i0, i1)
@@ -631,14 +782,14 @@ class FusedNAdam(FusedOptimizer):
 
     def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  momentum_decay=4e-3, decoupled_weight_decay=False, grad_dtype=None,
-                 max_grad_norm=None):
+                 max_grad_norm=None, ema_decay=None):
         _check_adam_ranges("FusedNAdam", lr, betas, eps, weight_decay)
         if not 0.0 <= momentum_decay:
             raise ValueError(f"FusedNAdam: invalid momentum_decay value: {momentum_decay}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       momentum_decay=momentum_decay,
                                       decoupled_weight_decay=bool(decoupled_weight_decay)),
-                         grad_dtype, max_grad_norm)
+                         grad_dtype, max_grad_norm, ema_decay)
         self._mv_mu_key = None
         self._mv_mu_products = [1.0]      # P_0 .. P_t for _mv_mu_key = (beta1, momentum_decay)
 

@@ -177,6 +177,9 @@ def broadcast_optimizer_state(optimizer, root_rank: int = 0) -> None:
                 s = optimizer.state[p].get("step")
                 if torch.is_tensor(s):
                     a.step = int(s.item())
+                    e = optimizer.state[p].get("ema_updates")
+                    if a.ema is not None and torch.is_tensor(e):
+                        a.ema_updates = int(e.item())
                     break
             # the exact fp32 master was just broadcast: keep it.  Without this the
             # version bump of a preceding broadcast_parameters makes the next step

@@ -38,7 +38,10 @@ A fused optimizer's ``max_grad_norm`` is captured like the rest of the step (the
 norm pass, the finalize and the clipped updates are kernels on device operands),
 but its VALUE is a launch argument of the finalize kernel: the graph keeps the
 value it was captured with, and changing the attribute afterwards affects eager
-steps only.
+steps only.  ``ema_decay`` is captured in the same way: the eager warmup has already
+taken the copying first update of the weight average, so the captured update launches
+carry the decay as a launch argument, the graph keeps the value it was captured with,
+and the arenas' update counts advance per replay like their step counts.
 
 Measured (1x MI355X, ROCm 7): ResNet-50 replays are correct but not faster than
 eager at bs 128-1024 — the step is GPU-bound and ROCm replays the two-stream
@@ -133,6 +136,7 @@ class GraphedStep:
 
         # 2. capture with dyn-reading optimizer kernels; roll back host bookkeeping
         steps0 = [a.step for a in self.arenas]
+        ema0 = [a.ema_updates for a in self.arenas]
         bn0 = [m._mv_steps for m in self.bns]
         mvd0 = optimizer._mvd_steps if self.dist else 0
         self.graph = torch.cuda.CUDAGraph()
@@ -158,8 +162,10 @@ class GraphedStep:
             if inline:
                 optimizer._mvd_inline = False
         self.bn_incr = [m._mv_steps - s for m, s in zip(self.bns, bn0)]
-        for a, s in zip(self.arenas, steps0):
+        self.ema_incr = [a.ema_updates - e for a, e in zip(self.arenas, ema0)]
+        for a, s, e in zip(self.arenas, steps0, ema0):
             a.step = s
+            a.ema_updates = e
         for m, s in zip(self.bns, bn0):
             m._mv_steps = s
         if self.dist:
@@ -170,9 +176,10 @@ class GraphedStep:
     def __call__(self):
         k, host = self.ring.acquire()
         vals = []
-        for a in self.arenas:
+        for a, inc in zip(self.arenas, self.ema_incr):
             a.sync_master_if_modified()      # params edited in place since the last step
             a.step += 1
+            a.ema_updates += inc
             vals.extend(self.opt._mv_dyn_values(a))
         host.copy_(torch.tensor(vals, dtype=torch.float32))
         for i, a in enumerate(self.arenas):

@@ -377,6 +377,8 @@ class _DistributedOptimizerMixin:
                        self.max_grad_norm if self._mvd_fused else None)).encode())
         if self._mvd_accum_dtype is not None:       # default runs hash as they always did
             h.update(repr(("accumulation_dtype", str(self._mvd_accum_dtype))).encode())
+        if self._mvd_fused and self.ema_decay is not None:
+            h.update(repr(("ema_decay", float(self.ema_decay))).encode())
         for b in self._mvd_buckets:
             h.update(repr((str(b.arena.grad.dtype), b.hi - b.lo,
                            [(self._mvd_names[id(p)], tuple(p.shape)) for p in b.params])).encode())
@@ -541,7 +543,7 @@ class _DistributedOptimizerMixin:
                 for a in self._mvd_arenas:
                     mine = [b for b in plan if b.arena is a]
                     if mine and all(b in skipped for b in mine):
-                        a.step = max(a.step - 1, 0)   # no update of this arena counted
+                        self._mv_uncount_step(a)      # no update of this arena counted
             msg = f"mivod: non-finite gradients on the fp16 wire (or in the gradients) — {what}"
             if self._mvd_dynamic:
                 self._mvd_gs = max(self._mvd_gs * 0.5, 2.0 ** -24)
@@ -788,6 +790,16 @@ class _DistributedOptimizerMixin:
                 self._mvd_done_event = ev2
         b.launched = True
 
+    def _mv_ema_sync(self):
+        """ema_parameters() / ema_overwrite(): never between backward and step(), and after
+        everything the comm stream still holds (the last step's updates of weights and
+        average)."""
+        if self._mvd_in_step:
+            raise AssertionError("the EMA weights cannot be exchanged after loss.backward() but "
+                                 "before optimizer.step() or optimizer.synchronize()")
+        if self._mvd_stream is not None and torch.cuda.is_available():
+            torch.cuda.current_stream().wait_stream(self._mvd_stream)
+
     # ------------------------------------------------------- comm timing
     def _mvd_comm_event(self):
         if self._mvd_comm_log is None:
@@ -822,6 +834,8 @@ class _DistributedOptimizerMixin:
         self._mv_skip = self._mvd_bucket_flag(b) if self._mvd_guard else None
         with MK.range(f"mivod.step.{b.name}"):
             self._mv_apply(b.arena, b.i0, b.i1, gscale)
+            # the weight average rides behind the step: same stream, same skip flag
+            self._mv_apply_ema(b.arena, b.i0, b.i1)
         self._mv_skip = None
         if rec is not None:
             rec.add(b.name, "OPTIMIZER_STEP", t0, rec.event() if cuda else rec.host())
