@@ -72,6 +72,9 @@ def main():
     ap.add_argument("--ema-decay", type=float, default=None,
                     help="keep an fp32 moving average of the weights (FusedAdam's ema_decay); "
                          "default off")
+    ap.add_argument("--segments", type=int, default=0,
+                    help="pack K random-length sequences into every row (segment_ids: "
+                         "block-diagonal attention); default 0: one sequence per row")
     args = ap.parse_args()
     if args.gpus > 1 and not any(k in os.environ for k in ("WORLD_SIZE", "HOROVOD_RANK")):
         sys.path.insert(0, ROOT)
@@ -113,7 +116,7 @@ def main():
     hvd.broadcast_optimizer_state(opt, 0)
     g = torch.Generator(device=dev)
     g.manual_seed(100 + rank)
-    batch = synthetic_batch(cfg, args.batch, args.seq, dev, generator=g)
+    batch = synthetic_batch(cfg, args.batch, args.seq, dev, generator=g, segments=args.segments)
 
     comm_stream = hvd.comm_stream()
     timing = []
@@ -180,7 +183,7 @@ def main():
                        "optimizer": "mivod FusedAdamW", "max_grad_norm": args.max_grad_norm,
                        "backward_passes_per_step": passes,
                        "accumulation_dtype": args.accumulation_dtype,
-                       "ema_decay": args.ema_decay,
+                       "ema_decay": args.ema_decay, "segments_per_row": args.segments,
                        "transport": basics.state().backend if size > 1 else "local"},
             "comm": comm}), flush=True)
     hvd.shutdown()

@@ -1,4 +1,4 @@
-// Fused MFMA attention (head dim 64) launchers — mv_attn.hip.
+// Fused MFMA attention (head dim 64) launchers — mv_attn.hip, mv_attn_seg.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,6 +13,9 @@ struct AttnParams {
   float p_drop;         // attention-probability dropout
   uint32_t seed;
   uint32_t thresh;      // drop if the element's 16-bit hash < thresh (round(p_drop 2^16))
+  // packed sequences: [b, s] from mv_attn_seg_bounds, token t's run of equal segment ids as
+  // lo | hi << 16 (keys / queries [lo, hi); lo == hi: padding), or nullptr: dense
+  const uint32_t* seg;
 };
 
 void mv_attn_fwd(const AttnParams& p, hipStream_t st);
@@ -20,5 +23,13 @@ void mv_attn_fwd(const AttnParams& p, hipStream_t st);
 // dqkv over the tokens (the fused QKV projection's bias-gradient partials)
 void mv_attn_bwd(const AttnParams& p, const void* out, const void* dout, float* delta,
                  float* dq_part, void* dqkv, hipStream_t st, float* bsum = nullptr);
+// segment ids [b, s] (int32, or int64 with ids64) -> bounds [b, s]; s <= 65535.  One launch.
+void mv_attn_seg_bounds(const void* ids, bool ids64, uint32_t* bounds, int b, int s,
+                        hipStream_t st);
+// the p.seg != nullptr halves of mv_attn_fwd / mv_attn_bwd (which has run delta_kernel for
+// s > 128): mv_attn_seg.hip
+void mv_attn_seg_fwd(const AttnParams& p, hipStream_t st);
+void mv_attn_seg_bwd(const AttnParams& p, const void* out, const void* dout, const float* delta,
+                     float* dq_part, void* dqkv, hipStream_t st, float* bsum);
 void mv_attn_dropout_mask(int b, int h, int s, uint32_t seed, uint32_t thresh, uint8_t* keep,
                           hipStream_t st);

@@ -16,7 +16,7 @@ void check_mn(const char* fn, const char* what, const at::Tensor& t, const at::T
               t.numel());
 }
 
-// dropout threshold on a 16-bit uniform (mv_attn.hip drop_keep, mv_bert.hip keep8)
+// dropout threshold on a 16-bit uniform (mv_attn_kernels.h drop_keep, mv_bert.hip keep8)
 uint32_t drop_thresh(const char* fn, double p) {
   TORCH_CHECK(p >= 0.0 && p < 1.0, fn, ": dropout must be in [0, 1)");
   return (uint32_t)std::min(65535.0, std::floor(p * 65536.0 + 0.5));
@@ -25,8 +25,9 @@ uint32_t drop_thresh(const char* fn, double p) {
 // ---------------------------------------------------------------------------
 // Fused MFMA attention (head dim 64)
 // ---------------------------------------------------------------------------
+// seg: the int32 [b, s] run bounds of _attn_seg.seg_bounds (packed sequences), or none
 AttnParams attn_params(const char* fn, const at::Tensor& qkv, const OptTensor& mask, double p_drop,
-                       int64_t seed) {
+                       int64_t seed, const OptTensor& seg) {
   check_nd(fn, "qkv", qkv, qkv, 5);
   TORCH_CHECK(qkv.size(2) == 3 && qkv.size(4) == 64, fn, ": qkv must be [b, s, 3, h, 64]");
   AttnParams p{};
@@ -40,12 +41,37 @@ AttnParams attn_params(const char* fn, const at::Tensor& qkv, const OptTensor& m
   p.p_drop = (float)p_drop;
   p.seed = (uint32_t)seed;
   TORCH_CHECK(p.s <= 65536, fn, ": sequence length must be <= 65536 (dropout counter)");
+  if (given(seg)) {
+    TORCH_CHECK(seg->dim() == 2 && seg->size(0) == p.b && seg->size(1) == p.s, fn,
+                ": seg must be [b, s] = [", p.b, ", ", p.s, "]");
+    TORCH_CHECK(p.s <= 65535, fn, ": sequence length must be <= 65535 with segments (16-bit bounds)");
+    p.seg = reinterpret_cast<const uint32_t*>(
+        vec_ptr<int32_t>(fn, "seg", *seg, qkv, (int64_t)p.b * p.s));
+  }
   return p;
 }
 
-std::vector<at::Tensor> attn_fwd(at::Tensor qkv, c10::optional<at::Tensor> mask, double p_drop,
-                                 int64_t seed) {
-  AttnParams p = attn_params("attn_fwd", qkv, mask, p_drop, seed);
+// segment ids [b, s] (int32 or int64; negative = padding; every other id one contiguous run
+// per row, unchecked) -> int32 [b, s] run bounds lo | hi << 16 (mv_attn_seg.hip)
+at::Tensor attn_seg_bounds(at::Tensor ids) {
+  const char* fn = "attn_seg_bounds";
+  TORCH_CHECK(ids.is_cuda() && (ids.scalar_type() == at::kInt || ids.scalar_type() == at::kLong),
+              fn, ": segment_ids must be an int32 or int64 GPU tensor");
+  check_nd(fn, "segment_ids", ids, ids, 2, ids.scalar_type());
+  TORCH_CHECK(ids.size(1) >= 1 && ids.size(1) <= 65535, fn,
+              ": sequence length must be in [1, 65535] (16-bit bounds)");
+  c10::DeviceGuard guard(ids.device());
+  at::Tensor bounds = at::empty(ids.sizes(), ids.options().dtype(at::kInt));
+  if (ids.size(0) > 0)
+    mv_attn_seg_bounds(ids.data_ptr(), ids.scalar_type() == at::kLong,
+                       reinterpret_cast<uint32_t*>(bounds.data_ptr<int32_t>()), (int)ids.size(0),
+                       (int)ids.size(1), cur_stream());
+  return bounds;
+}
+
+std::vector<at::Tensor> attn_fwd(const char* fn, const at::Tensor& qkv, const OptTensor& mask,
+                                 double p_drop, int64_t seed, const OptTensor& seg) {
+  AttnParams p = attn_params(fn, qkv, mask, p_drop, seed, seg);
   c10::DeviceGuard guard(qkv.device());
   at::Tensor out = at::empty({p.b, p.s, p.h, 64}, qkv.options());
   at::Tensor lse = at::empty({p.b, p.h, p.s}, qkv.options().dtype(at::kFloat));
@@ -59,8 +85,8 @@ std::vector<at::Tensor> attn_fwd(at::Tensor qkv, c10::optional<at::Tensor> mask,
 std::vector<at::Tensor> attn_bwd(const char* fn, const at::Tensor& qkv, const at::Tensor& out,
                                  const at::Tensor& dout, const at::Tensor& lse,
                                  const OptTensor& mask, double p_drop, int64_t seed,
-                                 bool want_bsum) {
-  AttnParams p = attn_params(fn, qkv, mask, p_drop, seed);
+                                 const OptTensor& seg, bool want_bsum) {
+  AttnParams p = attn_params(fn, qkv, mask, p_drop, seed, seg);
   const int64_t bsh = (int64_t)p.b * p.s * p.h;
   check_mn(fn, "out", out, qkv, bsh, 64);
   check_mn(fn, "dout", dout, qkv, bsh, 64);
@@ -374,11 +400,16 @@ std::vector<at::Tensor> ln_bwd(at::Tensor dy, at::Tensor v, at::Tensor mean, at:
 
 void bind_bert(pybind11::module_& m) {
   using Opt = c10::optional<at::Tensor>;
-  m.def("attn_fwd", &attn_fwd, "fused MFMA attention forward -> (out [b,s,h,64], lse)");
+  m.def("attn_fwd",
+        [](at::Tensor qkv, Opt mask, double p_drop, int64_t seed) {
+          return attn_fwd("attn_fwd", qkv, mask, p_drop, seed, c10::nullopt);
+        },
+        "fused MFMA attention forward -> (out [b,s,h,64], lse)");
   m.def("attn_bwd",
         [](at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, Opt mask, double p_drop,
            int64_t seed) {
-          return attn_bwd("attn_bwd", qkv, out, dout, lse, mask, p_drop, seed, false)[0];
+          return attn_bwd("attn_bwd", qkv, out, dout, lse, mask, p_drop, seed, c10::nullopt,
+                          false)[0];
         },
         "fused MFMA attention backward -> dqkv");
   m.def("attn_dropout_mask", &attn_dropout_mask, "dropout keep-mask of the fused attention");
@@ -394,11 +425,36 @@ void bind_bert(pybind11::module_& m) {
   m.def("attn_bwd_bsum",
         [](at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, Opt mask, double p_drop,
            int64_t seed) {
-          return attn_bwd("attn_bwd_bsum", qkv, out, dout, lse, mask, p_drop, seed, true);
+          return attn_bwd("attn_bwd_bsum", qkv, out, dout, lse, mask, p_drop, seed, c10::nullopt,
+                          true);
         },
         "fused MFMA attention backward (s <= 128) -> (dqkv, per-(b, h) column sums [b, 3 h 64])");
   m.def("gemm_gelu_bwd", &gemm_gelu_bwd,
         "(dy, W^T, pre, bias) -> (d_pre, dbias): dy . W with gelu(pre + bias)'s backward fused");
   m.def("ln_fwd", &ln_fwd, "v = res + dropout(z + b); y = LN(v) -> (y, v, mean, rstd)");
   m.def("ln_bwd", &ln_bwd, "-> (dv, dz, dgamma, dbeta, dbias)");
+  // the top-level surface is a snapshot (tests/mvk_api.json): block-diagonal attention for
+  // packed sequences is mivod._mvk._attn_seg — the three attention entry points with the
+  // run bounds of seg_bounds as a trailing operand
+  pybind11::module_ sg = m.def_submodule(
+      "_attn_seg", "fused MFMA attention over packed sequences (block-diagonal by segment id)");
+  sg.def("seg_bounds", &attn_seg_bounds,
+         "segment ids [b, s] (int32 / int64, negative = padding) -> run bounds int32 [b, s]");
+  sg.def("fwd",
+         [](at::Tensor qkv, Opt mask, double p_drop, int64_t seed, at::Tensor seg) {
+           return attn_fwd("_attn_seg.fwd", qkv, mask, p_drop, seed, seg);
+         },
+         "attn_fwd within each token's run -> (out [b,s,h,64], lse)");
+  sg.def("bwd",
+         [](at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, Opt mask,
+            double p_drop, int64_t seed, at::Tensor seg) {
+           return attn_bwd("_attn_seg.bwd", qkv, out, dout, lse, mask, p_drop, seed, seg, false)[0];
+         },
+         "attn_bwd within each token's run -> dqkv");
+  sg.def("bwd_bsum",
+         [](at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, Opt mask,
+            double p_drop, int64_t seed, at::Tensor seg) {
+           return attn_bwd("_attn_seg.bwd_bsum", qkv, out, dout, lse, mask, p_drop, seed, seg, true);
+         },
+         "attn_bwd_bsum within each token's run (s <= 128) -> (dqkv, column sums [b, 3 h 64])");
 }

@@ -28,6 +28,11 @@ BUILD = os.path.join(ROOT, "build", "native")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("MIVOD_OFFLOAD_ARCH", "gfx950")
 EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
+# extra device flags per kernel unit.  mv_attn_seg.hip: scalar fp32 VALU code only (no
+# v_pk_*_f32 selection); the older units keep the flags they were tuned and measured with
+HIP_UNIT_FLAGS = {
+    "mv_attn_seg.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _hipcc() -> str:
@@ -105,7 +110,8 @@ def build_kernels(verbose: bool = False, force: bool = False) -> str:
         objs.append(obj)
         if force or _stale(obj, [src] + hdrs):
             jobs.append([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
-                         "-munsafe-fp-atomics", "-I", kdir, "-c", src, "-o", obj])
+                         "-munsafe-fp-atomics"] + HIP_UNIT_FLAGS.get(f, [])
+                        + ["-I", kdir, "-c", src, "-o", obj])
     for f in cpp_srcs:
         src = os.path.join(kdir, f)
         obj = os.path.join(BUILD, f + ".o")

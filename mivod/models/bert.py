@@ -91,7 +91,7 @@ class BertSelfAttention(nn.Module):
         self.dropout = nn.Dropout(c.hidden_dropout_prob)
         self.LayerNorm = nn.LayerNorm(c.hidden_size, eps=c.layer_norm_eps)
 
-    def forward(self, x, mask_bias):
+    def forward(self, x, mask_bias, seg=None):
         from ..ops.attention import BiasGradSlot, attention
         b, s, hd = x.shape
         # the QKV bias gradient comes out of the attention backward kernel (BiasGradSlot)
@@ -99,7 +99,7 @@ class BertSelfAttention(nn.Module):
         qkv = linear(x, self.qkv.weight, self.qkv.bias, bias_slot=slot).view(b, s, 3, self.h,
                                                                              self.d)
         ctx = attention(qkv, mask_bias, self.p_attn if self.training else 0.0,
-                        bias_slot=slot)   # [b, s, h*d]
+                        bias_slot=slot, segment_bounds=seg)   # [b, s, h*d]
         # dense GEMM without bias; bias + dropout + residual + LayerNorm fused; the
         # residual use of x is tapped: its gradient joins x's producer LN backward
         return bias_dropout_add_ln(linear(ctx, self.dense.weight), self.dense.bias, tap(x),
@@ -115,8 +115,8 @@ class BertLayer(nn.Module):
         self.dropout = nn.Dropout(c.hidden_dropout_prob)
         self.LayerNorm = nn.LayerNorm(c.hidden_size, eps=c.layer_norm_eps)
 
-    def forward(self, x, mask_bias):
-        a = self.attention(x, mask_bias)
+    def forward(self, x, mask_bias, seg=None):
+        a = self.attention(x, mask_bias, seg)
         # intermediate bias-GELU + down projection: one fused backward GEMM (ops/linear.py)
         y = gelu_linear(linear(a, self.intermediate.weight), self.intermediate.bias,
                         self.output.weight)
@@ -132,8 +132,15 @@ class BertModel(nn.Module):
         self.layers = nn.ModuleList([BertLayer(c) for _ in range(c.num_hidden_layers)])
         self.pooler = nn.Linear(c.hidden_size, c.hidden_size)
 
-    def forward(self, input_ids, token_type_ids, attention_mask=None):
+    def forward(self, input_ids, token_type_ids, attention_mask=None, segment_ids=None):
+        """``segment_ids`` [b, s]: several sequences packed into one row attend within
+        themselves only (ops.attention, "Packed sequences"); the run bounds are computed
+        once here for every layer.  Positions, the pooler and NSP stay per row."""
         x = self.embeddings(input_ids, token_type_ids)
+        seg = None
+        if segment_ids is not None:
+            from ..ops.attention import segment_bounds
+            seg = segment_bounds(segment_ids)
         # built whenever a mask is given — no data-dependent host sync per forward
         # (packed pre-training batches pass attention_mask=None: every token valid)
         mask_bias = None
@@ -148,7 +155,7 @@ class BertModel(nn.Module):
                                              lyr.intermediate.weight, lyr.output.weight)])
         try:
             for lyr in self.layers:
-                x = lyr(x, mask_bias)
+                x = lyr(x, mask_bias, seg)
         finally:
             if prep:
                 end_dgrad_weights()
@@ -182,10 +189,11 @@ class BertForPreTraining(nn.Module):
             nn.init.zeros_(m.bias)
 
     def forward(self, input_ids, token_type_ids, attention_mask, masked_positions,
-                masked_labels, nsp_labels):
+                masked_labels, nsp_labels, segment_ids=None):
         """Returns the pre-training loss.  ``masked_positions`` [b, m] index the
         masked tokens; ``masked_labels`` [b, m] (-100 = padding)."""
-        seq, pooled = self.bert(input_ids, token_type_ids, attention_mask)
+        seq, pooled = self.bert(input_ids, token_type_ids, attention_mask,
+                                segment_ids=segment_ids)
         b, m = masked_positions.shape
         idx = masked_positions + torch.arange(b, device=seq.device)[:, None] * seq.shape[1]
         sel = seq.reshape(-1, seq.shape[-1]).index_select(0, idx.reshape(-1))
@@ -198,10 +206,21 @@ class BertForPreTraining(nn.Module):
         return mlm + nsp
 
 
+def synthetic_segments(batch: int, seq: int, k: int, device, generator=None):
+    """Segment ids [batch, seq] (int32) of ``k`` runs of random lengths >= 1 per row."""
+    assert 1 <= k <= seq
+    cuts = torch.stack([torch.randperm(seq - 1, device=device, generator=generator)[:k - 1] + 1
+                        for _ in range(batch)])                          # k - 1 distinct run starts
+    start = torch.zeros(batch, seq, dtype=torch.int32, device=device)
+    start.scatter_(1, cuts, 1)
+    return start.cumsum(1, dtype=torch.int32)
+
+
 def synthetic_batch(c: BertConfig, batch: int, seq: int, device, mask_frac=0.15,
-                    generator=None, with_mask: bool = False):
+                    generator=None, with_mask: bool = False, segments: int = 0):
     """Synthetic pre-training batch of full-length (packed) sequences: the
-    attention mask is None (every position valid) unless ``with_mask``."""
+    attention mask is None (every position valid) unless ``with_mask``.  ``segments=k``
+    appends segment ids of ``k`` random-length runs per row (``synthetic_segments``)."""
     g = generator
     ids = torch.randint(0, c.vocab_size, (batch, seq), device=device, generator=g)
     tt = torch.zeros(batch, seq, dtype=torch.long, device=device)
@@ -212,6 +231,8 @@ def synthetic_batch(c: BertConfig, batch: int, seq: int, device, mask_frac=0.15,
                        for _ in range(batch)]).sort(dim=1).values
     labels = torch.randint(0, c.vocab_size, (batch, m), device=device, generator=g)
     nsp = torch.randint(0, 2, (batch,), device=device, generator=g)
+    if segments:
+        return ids, tt, am, pos, labels, nsp, synthetic_segments(batch, seq, segments, device, g)
     return ids, tt, am, pos, labels, nsp
 
 

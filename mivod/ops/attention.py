@@ -22,6 +22,19 @@ and yields NaN for such a row; only the kernels define it.  Other finite values
 below about -4e37 are not a supported way to say "masked" (the s <= 128 forward multiplies the
 mask by 8 ahead of the common score scale and overflows earlier than the other kernels): use ``-inf``, ``finfo.min``
 or a moderate value like -10000.
+
+Packed sequences
+----------------
+``segment_ids`` is an integer tensor ``[b, s]``: query i and key j of a batch row attend to each
+other iff ``segment_ids[i] == segment_ids[j]`` and that id is ``>= 0`` (a block-diagonal mask;
+``mask_bias`` still applies on top).  A negative id marks padding: such a token is no key for
+anyone, and as a query it is a fully masked row in the sense above (``out = 0``, zero
+gradients).  On the kernel path every non-negative id must occupy ONE contiguous run of its row
+(padding may sit anywhere); this is the caller's contract and is not checked on the device.
+``segment_bounds(segment_ids)`` turns the ids into per-token run bounds in one launch: compute it
+once per model forward and pass ``segment_bounds=`` to every layer.  The kernels skip the tiles
+outside a run (docs/PACKED_ATTENTION.md).  ``attention_math`` builds the mask from id equality,
+so it is correct for any ids, and gives padding queries 0 like the kernels.
 """
 from __future__ import annotations
 
@@ -35,16 +48,23 @@ from . import kernels as K
 
 
 def attention_math(qkv: torch.Tensor, mask_bias=None, p_drop: float = 0.0,
-                   keep_mask=None) -> torch.Tensor:
+                   keep_mask=None, segment_ids=None) -> torch.Tensor:
     """The fallback for devices and dtypes the kernels do not cover.  A row whose keys are all
     masked with ``-inf`` comes out NaN here (softmax of an empty set), where the kernels give
-    0: see the mask contract above."""
+    0: see the mask contract above.  With ``segment_ids`` (any ids, contiguous or not) the
+    queries without a key — padding — get 0 instead."""
     b, s, _, h, d = qkv.shape
     q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)          # [b, h, s, d]
     scores = torch.matmul(q, k.transpose(-1, -2)).float() * (1.0 / math.sqrt(d))
     if mask_bias is not None:
         scores = scores + mask_bias.float().reshape(b, 1, 1, s)
+    if segment_ids is not None:
+        ids = segment_ids.reshape(b, s)
+        same = (ids[:, :, None] == ids[:, None, :]) & (ids >= 0)[:, None, :]      # [b, q, k]
+        scores = scores.masked_fill(~same[:, None], -math.inf)
     p = torch.softmax(scores, dim=-1)
+    if segment_ids is not None:
+        p = torch.nan_to_num(p, nan=0.0)                    # a query with no key at all
     if keep_mask is not None:
         p = p * keep_mask.to(p.dtype) / (1.0 - p_drop)
     elif p_drop > 0:
@@ -66,9 +86,13 @@ class BiasGradSlot:
 
 class _FusedAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, mask, p_drop, seed, slot=None):
-        out, lse = K.native().attn_fwd(qkv, mask, float(p_drop), int(seed))
-        ctx.save_for_backward(qkv, out, lse, mask)
+    def forward(ctx, qkv, mask, p_drop, seed, slot=None, seg=None):
+        nat = K.native()
+        if seg is None:
+            out, lse = nat.attn_fwd(qkv, mask, float(p_drop), int(seed))
+        else:
+            out, lse = nat._attn_seg.fwd(qkv, mask, float(p_drop), int(seed), seg)
+        ctx.save_for_backward(qkv, out, lse, mask, seg)
         ctx.p_drop, ctx.seed = float(p_drop), int(seed)
         ctx.slot = slot
         b, s, h, d = out.shape
@@ -76,17 +100,22 @@ class _FusedAttention(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, out, lse, mask = ctx.saved_tensors
+        qkv, out, lse, mask, seg = ctx.saved_tensors
         dout = dout.contiguous().view(out.shape)
         if dout.dtype != torch.bfloat16:
             dout = dout.to(torch.bfloat16)
         nat = K.native()
-        if ctx.slot is not None and qkv.shape[1] <= 128:
-            dqkv, ctx.slot.partials = nat.attn_bwd_bsum(qkv, out, dout, lse, mask, ctx.p_drop,
-                                                        ctx.seed)
+        args = (qkv, out, dout, lse, mask, ctx.p_drop, ctx.seed)
+        bsum = ctx.slot is not None and qkv.shape[1] <= 128
+        if seg is not None:
+            res = (nat._attn_seg.bwd_bsum if bsum else nat._attn_seg.bwd)(*args, seg)
         else:
-            dqkv = nat.attn_bwd(qkv, out, dout, lse, mask, ctx.p_drop, ctx.seed)
-        return dqkv, None, None, None, None
+            res = (nat.attn_bwd_bsum if bsum else nat.attn_bwd)(*args)
+        if bsum:
+            dqkv, ctx.slot.partials = res
+        else:
+            dqkv = res
+        return dqkv, None, None, None, None, None
 
 
 def fused_available(qkv: torch.Tensor) -> bool:
@@ -101,15 +130,52 @@ def mask_to_key_bias(mask_bias, b, s):
     return mask_bias.reshape(b, s).float().contiguous()
 
 
+class SegmentBounds:
+    """What ``segment_bounds`` returns: the ids, and on the kernel path their per-token run
+    bounds (int32 ``[b, s]``, ``lo | hi << 16``; None where only ``attention_math`` can run)."""
+    __slots__ = ("ids", "bounds")
+
+    def __init__(self, ids, bounds):
+        self.ids, self.bounds = ids, bounds
+
+
+def segment_bounds(segment_ids: torch.Tensor) -> SegmentBounds:
+    """Prepare ``segment_ids`` ``[b, s]`` for ``attention(..., segment_bounds=)``: one small
+    kernel launch on the GPU (no host sync), shared by every layer and both directions."""
+    if segment_ids.dim() != 2 or segment_ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError("segment_ids must be an int32 or int64 tensor [b, s]")
+    bounds = None
+    if segment_ids.is_cuda and fusion.on("attention"):
+        bounds = K.native()._attn_seg.seg_bounds(segment_ids.contiguous())
+    return SegmentBounds(segment_ids, bounds)
+
+
+_prepare_segments = segment_bounds      # attention() has a keyword of the same name
+
+
 def attention(qkv: torch.Tensor, mask_bias=None, p_drop: float = 0.0, seed=None,
-              bias_slot: "BiasGradSlot" = None) -> torch.Tensor:
+              bias_slot: "BiasGradSlot" = None, segment_ids=None,
+              segment_bounds: "SegmentBounds" = None) -> torch.Tensor:
     """``bias_slot``: the slot the projection that produced ``qkv`` was given
     (``ops.linear.linear(..., bias_slot=)``) — its bias gradient then comes out of this
-    op's backward kernel."""
+    op's backward kernel.  ``segment_ids`` or (computed once for all layers)
+    ``segment_bounds``: packed sequences, see the module docstring."""
+    if segment_ids is not None and segment_bounds is not None:
+        raise ValueError("pass segment_ids or segment_bounds, not both")
+    if segment_ids is not None:
+        segment_bounds = _prepare_segments(segment_ids)
+    b, s = qkv.shape[0], qkv.shape[1]
+    if segment_bounds is not None and tuple(segment_bounds.ids.shape) != (b, s):
+        raise ValueError(f"segment ids must be [b, s] = [{b}, {s}]")
     if fused_available(qkv):
-        b, s = qkv.shape[0], qkv.shape[1]
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0 else 0
+        seg = None
+        if segment_bounds is not None:
+            if segment_bounds.bounds is None:
+                raise RuntimeError("segment_bounds was prepared off the kernel path")
+            seg = segment_bounds.bounds
         return _FusedAttention.apply(qkv.contiguous(), mask_to_key_bias(mask_bias, b, s),
-                                     p_drop, seed, bias_slot)
-    return attention_math(qkv, mask_bias, p_drop)
+                                     p_drop, seed, bias_slot, seg)
+    return attention_math(qkv, mask_bias, p_drop,
+                          segment_ids=None if segment_bounds is None else segment_bounds.ids)

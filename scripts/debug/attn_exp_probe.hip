@@ -4,6 +4,7 @@
 //   for e in 0 1; do hipcc --offload-arch=gfx950 -O3 -std=c++17 -DMV_ATTN_RAW_EXP=$e \
 //     -DMV_ATTN_PROBE -I csrc/kernels scripts/debug/attn_exp_probe.hip -o /tmp/attn_probe_$e; done
 #include "../../csrc/kernels/mv_attn.hip"
+#include "../../csrc/kernels/mv_attn_seg.hip"      // mv_attn_fwd links against the segmented launchers
 
 #include <cmath>
 #include <cstdio>
