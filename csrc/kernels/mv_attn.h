@@ -1,4 +1,5 @@
-// Fused MFMA attention (head dim 64) launchers — mv_attn.hip, mv_attn_seg.hip.
+// Fused MFMA attention (head dim 64) launchers — mv_attn.hip, mv_attn_seg.hip,
+// mv_attn_causal.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,5 +32,13 @@ void mv_attn_seg_bounds(const void* ids, bool ids64, uint32_t* bounds, int b, in
 void mv_attn_seg_fwd(const AttnParams& p, hipStream_t st);
 void mv_attn_seg_bwd(const AttnParams& p, const void* out, const void* dout, const float* delta,
                      float* dq_part, void* dqkv, hipStream_t st, float* bsum);
+// delta[b, h, s] = rowsum(dO * out): the first pass of every s > 128 backward (mv_attn.hip)
+void mv_attn_delta(const AttnParams& p, const void* out, const void* dout, float* delta,
+                   hipStream_t st);
+// causal attention, key j <= query i, within the run where p.seg is given (else dense lower-
+// triangular, no bounds read): mv_attn_causal.hip.  The operands of mv_attn_fwd / mv_attn_bwd.
+void mv_attn_causal_fwd(const AttnParams& p, hipStream_t st);
+void mv_attn_causal_bwd(const AttnParams& p, const void* out, const void* dout, float* delta,
+                        float* dq_part, void* dqkv, hipStream_t st, float* bsum = nullptr);
 void mv_attn_dropout_mask(int b, int h, int s, uint32_t seed, uint32_t thresh, uint8_t* keep,
                           hipStream_t st);

@@ -54,6 +54,14 @@ void mv_attn_fwd(const AttnParams& p, hipStream_t st) {
   hipLaunchKernelGGL(fwd_kernel<false>, grid, dim3(256), 0, st, p);
 }
 
+void mv_attn_delta(const AttnParams& p, const void* out, const void* dout, float* delta,
+                   hipStream_t st) {
+  const int64_t rows = (int64_t)p.b * p.s * p.h;
+  static_assert(D == 64, "delta_kernel maps 8 lanes x 8 elements onto a row");
+  hipLaunchKernelGGL(delta_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st,
+                     (const __bf16*)out, (const __bf16*)dout, delta, p.b, p.s, p.h);
+}
+
 void mv_attn_bwd(const AttnParams& p, const void* out, const void* dout, float* delta,
                  float* dq_part, void* dqkv, hipStream_t st, float* bsum) {
   if (p.s <= 2 * KB) {   // one workgroup per (b, h): no delta / dq_reduce passes
@@ -63,9 +71,7 @@ void mv_attn_bwd(const AttnParams& p, const void* out, const void* dout, float* 
     return;
   }
   const int64_t rows = (int64_t)p.b * p.s * p.h;
-  static_assert(D == 64, "delta_kernel maps 8 lanes x 8 elements onto a row");
-  hipLaunchKernelGGL(delta_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st,
-                     (const __bf16*)out, (const __bf16*)dout, delta, p.b, p.s, p.h);
+  mv_attn_delta(p, out, dout, delta, st);
   if (p.seg) return mv_attn_seg_bwd(p, out, dout, delta, dq_part, dqkv, st, bsum);
   const int nkb = (p.s + KB - 1) / KB;
   hipLaunchKernelGGL(bwd_kernel<false>, dim3(nkb, p.b * p.h), dim3(256), 0, st, p,

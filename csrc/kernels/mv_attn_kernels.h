@@ -39,8 +39,15 @@
 // a wave (or workgroup) skips every 16-, 32- or 64-wide unit outside the union of its
 // ranges: such a unit contributes exactly zero.
 //
+// Causal attention (CAUSAL = true, docs/CAUSAL_ATTENTION.md): query i sees key j iff j <= i
+// (and, with SEG, j is in i's run).  The relation is no longer symmetric, so the ranges are
+// built per direction — the keys of query q are [lo, min(hi, q + 1)), the queries of key k
+// are [max(lo, k), hi); without SEG [0, q + 1) and [k, s), from lane ids alone — and the
+// same unions and skips then cut the work to the triangle.
+//
 // This header holds the kernel templates.  mv_attn.hip instantiates the dense kernels
-// (SEG = false: the code as it was) and mv_attn_seg.hip the segmented ones.
+// (SEG = CAUSAL = false: the code as it was), mv_attn_seg.hip the segmented ones and
+// mv_attn_causal.hip the two causal forms.
 #pragma once
 #include "mv_mfma.h"
 #include "mv_attn.h"
@@ -149,6 +156,27 @@ __device__ __forceinline__ Range seg_range(const uint32_t* seg, int bi, int t, i
   const int lo = (int)(wd & 0xFFFFu), hi = (int)(wd >> 16);
   return lo < hi ? Range{lo, hi} : Range{INT_MAX, 0};
 }
+// The keys query q attends (forward) and the queries that attend key k (backward).  SEG: the
+// token's run; CAUSAL cuts it at the diagonal, on the side the direction looks from.  A
+// token of a run lies inside its run, so the cut leaves at least the token itself, and an
+// empty run stays [INT_MAX, 0).  Without SEG the run is [0, s): no load of p.seg.
+template <bool SEG>
+__device__ __forceinline__ Range run_of(const uint32_t* seg, int bi, int t, int s) {
+  if constexpr (SEG) return seg_range(seg, bi, t, s);
+  return t < s ? Range{0, s} : Range{INT_MAX, 0};
+}
+template <bool SEG, bool CAUSAL>
+__device__ __forceinline__ Range keys_of(const uint32_t* seg, int bi, int q, int s) {
+  Range r = run_of<SEG>(seg, bi, q, s);
+  if constexpr (CAUSAL) r.hi = min(r.hi, q + 1);
+  return r;
+}
+template <bool SEG, bool CAUSAL>
+__device__ __forceinline__ Range queries_of(const uint32_t* seg, int bi, int k, int s) {
+  Range r = run_of<SEG>(seg, bi, k, s);
+  if constexpr (CAUSAL) r.lo = max(r.lo, k);
+  return r;
+}
 // union over the 16 lanes c of a wave whose lane groups g hold the same 16 ranges, as
 // wave-uniform scalars: the skips below are uniform branches
 __device__ __forceinline__ Range wave_union(Range r) {
@@ -156,6 +184,15 @@ __device__ __forceinline__ Range wave_union(Range r) {
   for (int m = 1; m < 16; m <<= 1) {
     r.lo = min(r.lo, __shfl_xor(r.lo, m, 64));
     r.hi = max(r.hi, __shfl_xor(r.hi, m, 64));
+  }
+  return Range{__builtin_amdgcn_readfirstlane(r.lo), __builtin_amdgcn_readfirstlane(r.hi)};
+}
+// intersection over the same 16 lanes: a unit inside it needs no element mask in any lane
+__device__ __forceinline__ Range wave_inter(Range r) {
+#pragma unroll
+  for (int m = 1; m < 16; m <<= 1) {
+    r.lo = max(r.lo, __shfl_xor(r.lo, m, 64));
+    r.hi = min(r.hi, __shfl_xor(r.hi, m, 64));
   }
   return Range{__builtin_amdgcn_readfirstlane(r.lo), __builtin_amdgcn_readfirstlane(r.hi)};
 }
@@ -188,12 +225,21 @@ __device__ int g_probe_bh = -1, g_probe_q = -1;
 #endif
 
 // ---------------------------------------------------------------- forward
-template <bool SEG>
+// CAUSAL: query block x costs x + 1 key blocks, so blockIdx.x counts the query blocks DOWN
+// (the heavy workgroups launch first and the light ones fill the tail), rotated by the (b, h)
+// index: workgroups go to the 8 XCDs round-robin, so with a fixed map and nqb a multiple of
+// 8 one XCD would get the heaviest block of every (b, h) (measured: docs/CAUSAL_ATTENTION.md;
+// the workgroups of one (b, h) stay neighbours in launch order, as in the dense grid); the key-block loop
+// ends at the diagonal block (br.hi); a block inside the INTERSECTION of the wave's 16 ranges
+// (wi: every block below the diagonal one, within the run) takes the unmasked path through a
+// uniform branch, so only the diagonal block (and a run's edge blocks) pays the compares.
+template <bool SEG, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void fwd_kernel(AttnParams p) {
+  constexpr bool M = SEG || CAUSAL;       // ranged: the Range machinery is live
   const int bh = blockIdx.y;
   const int bi = bh / p.h, hi = bh % p.h;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, g = l >> 4, c = l & 15;
-  const int q0 = blockIdx.x * QB + w * 16;
+  const int q0 = (CAUSAL ? gridDim.x - 1 - (blockIdx.x + blockIdx.y) % gridDim.x : blockIdx.x) * QB + w * 16;
   const int64_t tok = 3LL * p.h * D;
   const __bf16* Qb = ((const __bf16*)p.qkv) + (int64_t)bi * p.s * tok + (int64_t)hi * D;
   const __bf16* Kb = Qb + (int64_t)p.h * D;
@@ -218,14 +264,15 @@ __global__ __launch_bounds__(256) void fwd_kernel(AttnParams p) {
   // workgroup's 64: the key-block loop covers br only (the blocks left out are not staged),
   // and a wave sits out a staged block outside wr.  A block whose scores are all -inf
   // leaves m_run, l_run and O as they were (alpha = 1, e = 0), so leaving it out is exact.
-  Range qr{0, p.s}, wr{0, p.s}, br{0, p.s};
-  if constexpr (SEG) {
+  Range qr{0, p.s}, wr{0, p.s}, br{0, p.s}, wi{0, 0};
+  if constexpr (M) {
     __shared__ int rng_s[8];
-    qr = seg_range(p.seg, bi, q0 + c, p.s);
+    qr = keys_of<SEG, CAUSAL>(p.seg, bi, q0 + c, p.s);
     wr = wave_union(qr);
+    if constexpr (CAUSAL) wi = wave_inter(qr);
     br = block_union<4>(wr, rng_s);
   }
-  const int kb_beg = SEG ? min(br.lo, p.s) / KB * KB : 0, kb_end = SEG ? br.hi : p.s;
+  const int kb_beg = M ? min(br.lo, p.s) / KB * KB : 0, kb_end = M ? br.hi : p.s;
 
   for (int kb0 = kb_beg; kb0 < kb_end; kb0 += KB) {
     __syncthreads();
@@ -245,20 +292,35 @@ __global__ __launch_bounds__(256) void fwd_kernel(AttnParams p) {
       *reinterpret_cast<bf16x8*>(&Vs[key][d0 + 8]) = v1;
     }
     __syncthreads();
-    if (SEG && !wr.meets(kb0, KB)) continue;
+    if (M && !wr.meets(kb0, KB)) continue;
     // S^T tiles: st[t][r] = score(key kb0 + 16t + 4g + r, query q0 + c)
     float sv[4][4];
+    if (CAUSAL && wi.lo <= kb0 && kb0 + KB <= wi.hi) {
+      // wholly below the wave's first query (and inside every run): the same tiles, no mask
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      f32x4v acc = {0.f, 0.f, 0.f, 0.f};
+      for (int t = 0; t < 4; ++t) {
+        f32x4v acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) acc = mfma(ld_b128(&Ks[16 * t + c][32 * ks + 8 * g]), qf[ks], acc);
+        for (int ks = 0; ks < 2; ++ks) acc = mfma(ld_b128(&Ks[16 * t + c][32 * ks + 8 * g]), qf[ks], acc);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = kb0 + 16 * t + 4 * g + r;
-        float v = acc[r] * p.scale_log2;
-        if (p.mask) v += (key < p.s ? p.mask[(int64_t)bi * p.s + key] : 0.f) * LOG2E;
-        sv[t][r] = (SEG ? qr.has(key) : key < p.s) ? v : -INFINITY;
+        for (int r = 0; r < 4; ++r) {
+          sv[t][r] = acc[r] * p.scale_log2;
+          if (p.mask) sv[t][r] += p.mask[(int64_t)bi * p.s + kb0 + 16 * t + 4 * g + r] * LOG2E;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        f32x4v acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) acc = mfma(ld_b128(&Ks[16 * t + c][32 * ks + 8 * g]), qf[ks], acc);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = kb0 + 16 * t + 4 * g + r;
+          float v = acc[r] * p.scale_log2;
+          if (p.mask) v += (key < p.s ? p.mask[(int64_t)bi * p.s + key] : 0.f) * LOG2E;
+          sv[t][r] = (M ? qr.has(key) : key < p.s) ? v : -INFINITY;
+        }
       }
     }
     float mb = -INFINITY;
@@ -339,9 +401,12 @@ __global__ __launch_bounds__(256) void fwd_kernel(AttnParams p) {
 // per instruction).
 // SEG: a wave computes only the 16-key score tiles (MFMAs, dropout hashes, exp) and the
 // 32-key P.V chunks that meet the union of its 16 queries' runs; the others hold P = 0.
-template <int OCC, bool SEG>
+// CAUSAL: that union ends at the wave's last query, so wave w computes key tiles 0 .. w only
+// (the triangle).  The waves are not re-mapped to balance it: docs/CAUSAL_ATTENTION.md.
+template <int OCC, bool SEG, bool CAUSAL = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(OCC))) void fwd_short_kernel(
     AttnParams p) {
+  constexpr bool M = SEG || CAUSAL;
   constexpr int SK = 2 * KB;
   const int bh = blockIdx.x;
   const int bi = bh / p.h, hi = bh % p.h;
@@ -367,8 +432,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(OCC))) void
       qf[ks] = q < p.s ? ld_b128(Qb + (int64_t)q * tok + 32 * ks + 8 * g) : zero8();
   }
   Range qr{0, p.s}, wr{0, p.s};       // SEG: the keys of this lane's query, of the wave's 16
-  if constexpr (SEG) {
-    qr = seg_range(p.seg, bi, q0 + c, p.s);
+  if constexpr (M) {
+    qr = keys_of<SEG, CAUSAL>(p.seg, bi, q0 + c, p.s);
     wr = wave_union(qr);
   }
   {  // 512 threads: key t / 4, dims 16 (t % 4) .. + 15 of K and of V
@@ -387,7 +452,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(OCC))) void
       kmask = 0u;
 #pragma unroll
       for (int tt = 0; tt < 8; ++tt) {
-        if (SEG && !wr.meets(16 * tt, 16)) continue;
+        if (M && !wr.meets(16 * tt, 16)) continue;
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
           const uint32_t kk = (uint32_t)(16 * tt + 4 * g + r);          // even
@@ -412,7 +477,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(OCC))) void
   float sv[8][4];
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
-    if (SEG && !wr.meets(16 * t, 16)) {       // no key of this tile in any of the wave's runs
+    if (M && !wr.meets(16 * t, 16)) {       // no key of this tile in any of the wave's runs
 #pragma unroll
       for (int r = 0; r < 4; ++r) sv[t][r] = -INFINITY;
       continue;
@@ -427,10 +492,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(OCC))) void
       const int key = 16 * t + 4 * g + r;
       float v = acc[r];
       if (p.mask) v += (key < p.s ? p.mask[(int64_t)bi * p.s + key] : 0.f) * (LOG2E / sc);
-      sv[t][r] = (!SEG || qr.has(key)) ? v : -INFINITY;       // hi <= s: covers keys past s
+      sv[t][r] = (!M || qr.has(key)) ? v : -INFINITY;       // hi <= s: covers keys past s
     }
   }
-  if (!SEG && p.s < SK) {
+  if (!M && p.s < SK) {
 #pragma unroll
     for (int t = 0; t < 8; ++t)
 #pragma unroll
@@ -448,7 +513,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(OCC))) void
   float lsum = 0.f;
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
-    if (SEG && !wr.meets(16 * t, 16)) {       // exp2(-inf) = 0 without the exp
+    if (M && !wr.meets(16 * t, 16)) {       // exp2(-inf) = 0 without the exp
 #pragma unroll
       for (int r = 0; r < 4; ++r) sv[t][r] = 0.f;
       continue;
@@ -497,7 +562,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(OCC))) void
 #pragma unroll
   for (int ch = 0; ch < 4; ++ch) {
     if (32 * ch >= p.s) break;
-    if (SEG && !wr.meets(32 * ch, 32)) continue;       // P = 0 on all 32 keys
+    if (M && !wr.meets(32 * ch, 32)) continue;       // P = 0 on all 32 keys
     const int t0 = 2 * ch, t1 = 2 * ch + 1;
     float a8[8] = {sv[t0][0], sv[t0][1], sv[t0][2], sv[t0][3],
                    sv[t1][0], sv[t1][1], sv[t1][2], sv[t1][3]};
@@ -540,14 +605,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(OCC))) void
 // dq_reduce_kernel<true> sums, per query, only the key blocks of that query's run, which
 // are exactly the ones that covered it.  A key block of padding runs no query block and
 // stores zero dK / dV rows.
-template <bool SEG>
+// CAUSAL: key block kb runs the query blocks from its own to the end (of the run), so
+// blockIdx.x is already heavy-first: block 0 has the longest loop; it is rotated by the
+// (b, h) index for the XCDs like fwd_kernel's.  Tiles and chunks above
+// the diagonal of the first block are skipped like the tiles outside a run, and
+// dq_reduce_kernel<SEG, true> stops at each query's own key block.
+template <bool SEG, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void bwd_kernel(AttnParams p, const __bf16* __restrict__ dout,
                                                    const float* __restrict__ delta,
                                                    float* __restrict__ dq_part,
                                                    __bf16* __restrict__ dqkv) {
+  constexpr bool M = SEG || CAUSAL;
   const int bh = blockIdx.y;
   const int bi = bh / p.h, hi = bh % p.h;
-  const int kb = blockIdx.x;
+  const int kb = CAUSAL ? (blockIdx.x + blockIdx.y) % gridDim.x : blockIdx.x;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, g = l >> 4, c = l & 15;
   const int k0 = kb * KB + w * 16;
   const int64_t tok = 3LL * p.h * D;
@@ -597,13 +668,13 @@ __global__ __launch_bounds__(256) void bwd_kernel(AttnParams p, const __bf16* __
   const int nkb = (p.s + KB - 1) / KB;
   // SEG: kr = the queries of this lane's key, wr = of the wave's 16 keys, br = of the block's 64
   Range kr{0, p.s}, wr{0, p.s}, br{0, p.s};
-  if constexpr (SEG) {
+  if constexpr (M) {
     __shared__ int rng_s[8];
-    kr = seg_range(p.seg, bi, keyc, p.s);
+    kr = queries_of<SEG, CAUSAL>(p.seg, bi, keyc, p.s);
     wr = wave_union(kr);
     br = block_union<4>(wr, rng_s);
   }
-  const int qb_beg = SEG ? min(br.lo, p.s) / QB * QB : 0, qb_end = SEG ? br.hi : p.s;
+  const int qb_beg = M ? min(br.lo, p.s) / QB * QB : 0, qb_end = M ? br.hi : p.s;
 
   for (int qb0 = qb_beg; qb0 < qb_end; qb0 += QB) {
     __syncthreads();
@@ -637,7 +708,7 @@ __global__ __launch_bounds__(256) void bwd_kernel(AttnParams p, const __bf16* __
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int qt = 2 * ch + u;
-        if (SEG && !wr.meets(qb0 + 16 * qt, 16)) {       // none of these queries sees the wave's keys
+        if (M && !wr.meets(qb0 + 16 * qt, 16)) {       // none of these queries sees the wave's keys
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             zc[u][r] = dsc[u][r] = 0.f;
@@ -656,7 +727,7 @@ __global__ __launch_bounds__(256) void bwd_kernel(AttnParams p, const __bf16* __
         for (int r = 0; r < 4; ++r) {
           const int ql = 16 * qt + 4 * g + r;
           float pr = 0.f;
-          if (SEG ? kr.has(qb0 + ql) : keyc < p.s)
+          if (M ? kr.has(qb0 + ql) : keyc < p.s)
             pr = exp2f(sacc[r] * p.scale_log2 + kbias - lse_s[ql]);
           float z = pr, dzd = pacc[r];
           if (p.p_drop > 0.f) {
@@ -670,7 +741,7 @@ __global__ __launch_bounds__(256) void bwd_kernel(AttnParams p, const __bf16* __
           dSs[ql][w * 16 + c] = (__bf16)ds;
         }
       }
-      if (SEG && !wr.meets(qb0 + 32 * ch, 32)) continue;       // Z = dS = 0 on all 32 queries
+      if (M && !wr.meets(qb0 + 32 * ch, 32)) continue;       // Z = dS = 0 on all 32 queries
       float zb[8] = {zc[0][0], zc[0][1], zc[0][2], zc[0][3], zc[1][0], zc[1][1], zc[1][2], zc[1][3]};
       float sb[8] = {dsc[0][0], dsc[0][1], dsc[0][2], dsc[0][3],
                      dsc[1][0], dsc[1][1], dsc[1][2], dsc[1][3]};
@@ -738,12 +809,15 @@ __global__ __launch_bounds__(256) void bwd_kernel(AttnParams p, const __bf16* __
 // chunks that meet the union of its 16 keys' runs, stores dS = 0 for the others, and its
 // dQ product skips the 32-key steps outside the runs of its 16 queries (dS is 0 there).
 // Padding rows have dS = 0 throughout: they add 0 to every column sum.
-template <bool SEG>
+// CAUSAL: wave w's keys are seen by the query tiles from its own onward; the dQ product of
+// query tile qt stops at the 32-key step that holds its last query.
+template <bool SEG, bool CAUSAL = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void bwd_short_kernel(AttnParams p,
                                                          const __bf16* __restrict__ out,
                                                          const __bf16* __restrict__ dout,
                                                          __bf16* __restrict__ dqkv,
                                                          float* __restrict__ bsum) {
+  constexpr bool M = SEG || CAUSAL;
   constexpr int SK = 2 * KB;     // keys per workgroup
   const int bh = blockIdx.x;
   const int bi = bh / p.h, hi = bh % p.h;
@@ -842,8 +916,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void b
   const float kvalid = keyc < p.s ? 1.f : 0.f;
   // SEG: kr = the queries of this lane's key, wr = of the wave's 16 keys
   Range kr{0, p.s}, wr{0, p.s};
-  if constexpr (SEG) {
-    kr = seg_range(p.seg, bi, keyc, p.s);
+  if constexpr (M) {
+    kr = queries_of<SEG, CAUSAL>(p.seg, bi, keyc, p.s);
     wr = wave_union(kr);
   }
   // dropout keep bits of this lane's key for every query (s <= 128): bit 16 (q / 64) +
@@ -858,7 +932,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void b
     for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
       for (int qt = 0; qt < 4; ++qt) {
-        if (SEG && !wr.meets(64 * blk + 16 * qt, 16)) continue;
+        if (M && !wr.meets(64 * blk + 16 * qt, 16)) continue;
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
           const int r = rb + rr, bit = 16 * blk + 4 * qt + r;
@@ -889,7 +963,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void b
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int qt = 2 * ch + u;
-        if (SEG && !wr.meets(qb0 + 16 * qt, 16)) {       // none of these queries sees the wave's keys
+        if (M && !wr.meets(qb0 + 16 * qt, 16)) {       // none of these queries sees the wave's keys
 #pragma unroll
           for (int r = 0; r < 4; ++r) zc[u][r] = dsc[u][r] = 0.f;
           *reinterpret_cast<u32x2*>(&dSt[ks_off(keyc, 16 * qt + 4 * g)]) = u32x2{0u, 0u};
@@ -908,7 +982,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void b
           // SEG: a select, not the multiply — a score outside the query's run is not
           // bounded by its lse, and inf * 0 would be NaN
           const float ex = exp2f(sacc[r] * p.scale_log2 + kbias - lse4[qt][r]);
-          const float pr = SEG ? (kr.has(qb0 + 16 * qt + 4 * g + r) ? ex : 0.f) : ex * kvalid;
+          const float pr = M ? (kr.has(qb0 + 16 * qt + 4 * g + r) ? ex : 0.f) : ex * kvalid;
           float z = pr, dzd = pacc[r];
           if (p.p_drop > 0.f) {
             const bool kp = (kmask >> ((qb0 >> 2) + 4 * qt + r)) & 1u;
@@ -923,7 +997,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void b
         *reinterpret_cast<u32x2*>(&dSt[ks_off(keyc, 16 * qt + 4 * g)]) =
             u32x2{cvt_pk_bf16(dsc[u][0], dsc[u][1]), cvt_pk_bf16(dsc[u][2], dsc[u][3])};
       }
-      if (SEG && !wr.meets(qb0 + 32 * ch, 32)) continue;       // Z = dS = 0 on all 32 queries
+      if (M && !wr.meets(qb0 + 32 * ch, 32)) continue;       // Z = dS = 0 on all 32 queries
       float zb[8] = {zc[0][0], zc[0][1], zc[0][2], zc[0][3], zc[1][0], zc[1][1], zc[1][2], zc[1][3]};
       float sb[8] = {dsc[0][0], dsc[0][1], dsc[0][2], dsc[0][3],
                      dsc[1][0], dsc[1][1], dsc[1][2], dsc[1][3]};
@@ -940,14 +1014,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void b
     {
       const int qt = w & 3;
       Range dr{0, SK};                       // SEG: the keys of this wave's 16 dQ rows
-      if constexpr (SEG) dr = wave_union(seg_range(p.seg, bi, qb0 + 16 * qt + c, p.s));
+      if constexpr (M) dr = wave_union(keys_of<SEG, CAUSAL>(p.seg, bi, qb0 + 16 * qt + c, p.s));
 #pragma unroll
       for (int nn = 0; nn < 2; ++nn) {
         const int n = 2 * (w >> 2) + nn;
         f32x4v acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < SK / 32; ++ks) {
-          if (SEG && !dr.meets(32 * ks, 32)) continue;
+          if (M && !dr.meets(32 * ks, 32)) continue;
           acc = mfma(tr8_ks(ks_base(dSt, qt, g, c), ks), tr8_ks(ks_base(Ks, n, g, c), ks), acc);
         }
 #pragma unroll
@@ -1022,7 +1096,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void b
 
 // SEG: a query's partials exist only in the key blocks of its own run (bwd_kernel<true>
 // writes no others), summed in the same ascending order; a padding query sums none: dQ = 0
-template <bool SEG>
+// CAUSAL: and only up to the query's own key block q / KB (bwd_kernel<SEG, true> writes no
+// partial of a query block above a key block's diagonal)
+template <bool SEG, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void dq_reduce_kernel(const float* __restrict__ dq_part,
                                                          __bf16* __restrict__ dqkv, int nkb,
                                                          int b, int s, int h, float scale,
@@ -1037,6 +1113,10 @@ __global__ __launch_bounds__(256) void dq_reduce_kernel(const float* __restrict_
     k_beg = (int)(wd & 0xFFFFu) / KB;
     k_end = ((int)(wd >> 16) + KB - 1) / KB;
     if ((wd & 0xFFFFu) >= (wd >> 16)) k_end = k_beg;
+  }
+  if constexpr (CAUSAL) {
+    const int q = (int)((uint32_t)(i / D) / (uint32_t)h % (uint32_t)s);
+    k_end = min(k_end, q / KB + 1);
   }
   for (int k = k_beg; k < k_end; ++k) {
     float v[8];

@@ -69,15 +69,17 @@ at::Tensor attn_seg_bounds(at::Tensor ids) {
   return bounds;
 }
 
+// causal: key j <= query i on top of the other masks (mv_attn_causal.hip), here and in attn_bwd
 std::vector<at::Tensor> attn_fwd(const char* fn, const at::Tensor& qkv, const OptTensor& mask,
-                                 double p_drop, int64_t seed, const OptTensor& seg) {
+                                 double p_drop, int64_t seed, const OptTensor& seg,
+                                 bool causal = false) {
   AttnParams p = attn_params(fn, qkv, mask, p_drop, seed, seg);
   c10::DeviceGuard guard(qkv.device());
   at::Tensor out = at::empty({p.b, p.s, p.h, 64}, qkv.options());
   at::Tensor lse = at::empty({p.b, p.h, p.s}, qkv.options().dtype(at::kFloat));
   p.out = out.data_ptr();
   p.lse = lse.data_ptr<float>();
-  mv_attn_fwd(p, cur_stream());
+  (causal ? mv_attn_causal_fwd : mv_attn_fwd)(p, cur_stream());
   return {out, lse};
 }
 
@@ -85,7 +87,7 @@ std::vector<at::Tensor> attn_fwd(const char* fn, const at::Tensor& qkv, const Op
 std::vector<at::Tensor> attn_bwd(const char* fn, const at::Tensor& qkv, const at::Tensor& out,
                                  const at::Tensor& dout, const at::Tensor& lse,
                                  const OptTensor& mask, double p_drop, int64_t seed,
-                                 const OptTensor& seg, bool want_bsum) {
+                                 const OptTensor& seg, bool want_bsum, bool causal = false) {
   AttnParams p = attn_params(fn, qkv, mask, p_drop, seed, seg);
   const int64_t bsh = (int64_t)p.b * p.s * p.h;
   check_mn(fn, "out", out, qkv, bsh, 64);
@@ -102,9 +104,9 @@ std::vector<at::Tensor> attn_bwd(const char* fn, const at::Tensor& qkv, const at
   at::Tensor dq_part = at::empty({short_seq ? 1 : (int64_t)nkb * p.b * p.s * p.h * 64}, fo);
   at::Tensor dqkv = at::empty_like(qkv);
   at::Tensor bsum = want_bsum ? at::empty({p.b, 3LL * p.h * 64}, fo) : at::Tensor();
-  mv_attn_bwd(p, out.data_ptr(), dout.data_ptr(), delta.data_ptr<float>(),
-              dq_part.data_ptr<float>(), dqkv.data_ptr(), cur_stream(),
-              want_bsum ? bsum.data_ptr<float>() : nullptr);
+  (causal ? mv_attn_causal_bwd : mv_attn_bwd)(
+      p, out.data_ptr(), dout.data_ptr(), delta.data_ptr<float>(), dq_part.data_ptr<float>(),
+      dqkv.data_ptr(), cur_stream(), want_bsum ? bsum.data_ptr<float>() : nullptr);
   if (want_bsum) return {dqkv, bsum};
   return {dqkv};
 }
@@ -457,4 +459,33 @@ void bind_bert(pybind11::module_& m) {
            return attn_bwd("_attn_seg.bwd_bsum", qkv, out, dout, lse, mask, p_drop, seed, seg, true);
          },
          "attn_bwd_bsum within each token's run (s <= 128) -> (dqkv, column sums [b, 3 h 64])");
+  // causal attention, in a private submodule for the same reason: the three entry points
+  // with the run bounds as an OPTIONAL trailing operand (none: dense lower-triangular)
+  pybind11::module_ cg = m.def_submodule(
+      "_attn_causal", "fused MFMA causal attention (key <= query), alone or within packed runs");
+  cg.def("fwd",
+         [](at::Tensor qkv, Opt mask, double p_drop, int64_t seed, Opt seg) {
+           return attn_fwd("_attn_causal.fwd", qkv, mask, p_drop, seed, seg, true);
+         },
+         "causal attn_fwd -> (out [b,s,h,64], lse)", pybind11::arg("qkv"), pybind11::arg("mask"),
+         pybind11::arg("p_drop"), pybind11::arg("seed"), pybind11::arg("seg") = pybind11::none());
+  cg.def("bwd",
+         [](at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, Opt mask,
+            double p_drop, int64_t seed, Opt seg) {
+           return attn_bwd("_attn_causal.bwd", qkv, out, dout, lse, mask, p_drop, seed, seg, false,
+                           true)[0];
+         },
+         "causal attn_bwd -> dqkv", pybind11::arg("qkv"), pybind11::arg("out"),
+         pybind11::arg("dout"), pybind11::arg("lse"), pybind11::arg("mask"),
+         pybind11::arg("p_drop"), pybind11::arg("seed"), pybind11::arg("seg") = pybind11::none());
+  cg.def("bwd_bsum",
+         [](at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, Opt mask,
+            double p_drop, int64_t seed, Opt seg) {
+           return attn_bwd("_attn_causal.bwd_bsum", qkv, out, dout, lse, mask, p_drop, seed, seg,
+                           true, true);
+         },
+         "causal attn_bwd_bsum (s <= 128) -> (dqkv, column sums [b, 3 h 64])",
+         pybind11::arg("qkv"), pybind11::arg("out"), pybind11::arg("dout"), pybind11::arg("lse"),
+         pybind11::arg("mask"), pybind11::arg("p_drop"), pybind11::arg("seed"),
+         pybind11::arg("seg") = pybind11::none());
 }

@@ -30,8 +30,11 @@ ARCH = os.environ.get("MIVOD_OFFLOAD_ARCH", "gfx950")
 EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 # extra device flags per kernel unit.  mv_attn_seg.hip: scalar fp32 VALU code only (no
 # v_pk_*_f32 selection); the older units keep the flags they were tuned and measured with
+# mv_attn_causal.hip: the same, so that the <SEG, CAUSAL> kernels are built like their SEG twins
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_UNIT_FLAGS = {
-    "mv_attn_seg.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "mv_attn_seg.hip": _NO_PK_F32,
+    "mv_attn_causal.hip": _NO_PK_F32,
 }
 
 

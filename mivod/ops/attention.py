@@ -35,6 +35,19 @@ gradients).  On the kernel path every non-negative id must occupy ONE contiguous
 once per model forward and pass ``segment_bounds=`` to every layer.  The kernels skip the tiles
 outside a run (docs/PACKED_ATTENTION.md).  ``attention_math`` builds the mask from id equality,
 so it is correct for any ids, and gives padding queries 0 like the kernels.
+
+Causal attention
+----------------
+``causal=True``: query i attends key j iff ``j <= i`` and, with segments, j is in i's run;
+``mask_bias`` still applies on top.  Everything above holds unchanged: a key at ``-inf`` has
+probability exactly 0, a query with no key left (query 0 when key 0 is at ``-inf``) has
+``out = 0``, ``lse = -inf`` and zero gradients, padding tokens are exactly 0, and the dropout
+hash is the same function of the absolute (b h, query, key).  The kernels are the ``CAUSAL``
+instantiations in ``csrc/kernels/mv_attn_causal.hip``: without segments they read no bounds at
+all, with ``segment_bounds`` they take the same direction-free bounds and derive the keys of a
+query and the queries of a key from them, and they skip the tiles above the diagonal
+(docs/CAUSAL_ATTENTION.md).  ``attention_math(..., causal=True)`` puts ``-inf`` above the
+diagonal and gives a query with no key 0.
 """
 from __future__ import annotations
 
@@ -48,11 +61,11 @@ from . import kernels as K
 
 
 def attention_math(qkv: torch.Tensor, mask_bias=None, p_drop: float = 0.0,
-                   keep_mask=None, segment_ids=None) -> torch.Tensor:
+                   keep_mask=None, segment_ids=None, causal: bool = False) -> torch.Tensor:
     """The fallback for devices and dtypes the kernels do not cover.  A row whose keys are all
     masked with ``-inf`` comes out NaN here (softmax of an empty set), where the kernels give
     0: see the mask contract above.  With ``segment_ids`` (any ids, contiguous or not) the
-    queries without a key — padding — get 0 instead."""
+    queries without a key — padding — get 0 instead, and so they do with ``causal``."""
     b, s, _, h, d = qkv.shape
     q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)          # [b, h, s, d]
     scores = torch.matmul(q, k.transpose(-1, -2)).float() * (1.0 / math.sqrt(d))
@@ -62,8 +75,11 @@ def attention_math(qkv: torch.Tensor, mask_bias=None, p_drop: float = 0.0,
         ids = segment_ids.reshape(b, s)
         same = (ids[:, :, None] == ids[:, None, :]) & (ids >= 0)[:, None, :]      # [b, q, k]
         scores = scores.masked_fill(~same[:, None], -math.inf)
+    if causal:
+        above = torch.ones(s, s, dtype=torch.bool, device=scores.device).triu(1)
+        scores = scores.masked_fill(above, -math.inf)
     p = torch.softmax(scores, dim=-1)
-    if segment_ids is not None:
+    if segment_ids is not None or causal:
         p = torch.nan_to_num(p, nan=0.0)                    # a query with no key at all
     if keep_mask is not None:
         p = p * keep_mask.to(p.dtype) / (1.0 - p_drop)
@@ -86,15 +102,17 @@ class BiasGradSlot:
 
 class _FusedAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, mask, p_drop, seed, slot=None, seg=None):
+    def forward(ctx, qkv, mask, p_drop, seed, slot=None, seg=None, causal=False):
         nat = K.native()
-        if seg is None:
+        if causal:
+            out, lse = nat._attn_causal.fwd(qkv, mask, float(p_drop), int(seed), seg)
+        elif seg is None:
             out, lse = nat.attn_fwd(qkv, mask, float(p_drop), int(seed))
         else:
             out, lse = nat._attn_seg.fwd(qkv, mask, float(p_drop), int(seed), seg)
         ctx.save_for_backward(qkv, out, lse, mask, seg)
         ctx.p_drop, ctx.seed = float(p_drop), int(seed)
-        ctx.slot = slot
+        ctx.slot, ctx.causal = slot, bool(causal)
         b, s, h, d = out.shape
         return out.view(b, s, h * d)
 
@@ -107,7 +125,9 @@ class _FusedAttention(torch.autograd.Function):
         nat = K.native()
         args = (qkv, out, dout, lse, mask, ctx.p_drop, ctx.seed)
         bsum = ctx.slot is not None and qkv.shape[1] <= 128
-        if seg is not None:
+        if ctx.causal:
+            res = (nat._attn_causal.bwd_bsum if bsum else nat._attn_causal.bwd)(*args, seg)
+        elif seg is not None:
             res = (nat._attn_seg.bwd_bsum if bsum else nat._attn_seg.bwd)(*args, seg)
         else:
             res = (nat.attn_bwd_bsum if bsum else nat.attn_bwd)(*args)
@@ -115,7 +135,7 @@ class _FusedAttention(torch.autograd.Function):
             dqkv, ctx.slot.partials = res
         else:
             dqkv = res
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None
 
 
 def fused_available(qkv: torch.Tensor) -> bool:
@@ -155,11 +175,12 @@ _prepare_segments = segment_bounds      # attention() has a keyword of the same 
 
 def attention(qkv: torch.Tensor, mask_bias=None, p_drop: float = 0.0, seed=None,
               bias_slot: "BiasGradSlot" = None, segment_ids=None,
-              segment_bounds: "SegmentBounds" = None) -> torch.Tensor:
+              segment_bounds: "SegmentBounds" = None, causal: bool = False) -> torch.Tensor:
     """``bias_slot``: the slot the projection that produced ``qkv`` was given
     (``ops.linear.linear(..., bias_slot=)``) — its bias gradient then comes out of this
     op's backward kernel.  ``segment_ids`` or (computed once for all layers)
-    ``segment_bounds``: packed sequences, see the module docstring."""
+    ``segment_bounds``: packed sequences, see the module docstring.  ``causal``: key j <= query i
+    on top of the other masks."""
     if segment_ids is not None and segment_bounds is not None:
         raise ValueError("pass segment_ids or segment_bounds, not both")
     if segment_ids is not None:
@@ -176,6 +197,7 @@ def attention(qkv: torch.Tensor, mask_bias=None, p_drop: float = 0.0, seed=None,
                 raise RuntimeError("segment_bounds was prepared off the kernel path")
             seg = segment_bounds.bounds
         return _FusedAttention.apply(qkv.contiguous(), mask_to_key_bias(mask_bias, b, s),
-                                     p_drop, seed, bias_slot, seg)
+                                     p_drop, seed, bias_slot, seg, causal)
     return attention_math(qkv, mask_bias, p_drop,
-                          segment_ids=None if segment_bounds is None else segment_bounds.ids)
+                          segment_ids=None if segment_bounds is None else segment_bounds.ids,
+                          causal=causal)
