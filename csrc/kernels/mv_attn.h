@@ -1,5 +1,5 @@
-// Fused MFMA attention (head dim 64) launchers — mv_attn.hip, mv_attn_seg.hip,
-// mv_attn_causal.hip.
+// Fused MFMA attention launchers — head dim 64: mv_attn.hip, mv_attn_seg.hip,
+// mv_attn_causal.hip; head dim 128: mv_attn_d128.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,5 +40,11 @@ void mv_attn_delta(const AttnParams& p, const void* out, const void* dout, float
 void mv_attn_causal_fwd(const AttnParams& p, hipStream_t st);
 void mv_attn_causal_bwd(const AttnParams& p, const void* out, const void* dout, float* delta,
                         float* dq_part, void* dqkv, hipStream_t st, float* bsum = nullptr);
+// head dim 128 (mv_attn_d128.hip): the same AttnParams over qkv [b, s, 3, h, 128] and out
+// [b, s, h, 128], scale_log2 = log2(e) / sqrt(128); p.seg and causal select the form; any
+// s >= 1.  delta [b, h, s] fp32 is the backward's only scratch (no dQ partials, no bsum).
+void mv_attn_d128_fwd(const AttnParams& p, bool causal, hipStream_t st);
+void mv_attn_d128_bwd(const AttnParams& p, bool causal, const void* out, const void* dout,
+                      float* delta, void* dqkv, hipStream_t st);
 void mv_attn_dropout_mask(int b, int h, int s, uint32_t seed, uint32_t thresh, uint8_t* keep,
                           hipStream_t st);

@@ -1,5 +1,7 @@
 // mivod._mvk bindings: fused attention, embeddings, bias-GELU, cross entropy, LayerNorm
 // (mv_attn.h, mv_bert.h; gemm_gelu_bwd also runs mv_gemm.h's 256 x 256 kernel)
+#include <cmath>
+
 #include "mv_checks.h"
 #include "mv_attn.h"
 #include "mv_bert.h"
@@ -26,16 +28,17 @@ uint32_t drop_thresh(const char* fn, double p) {
 // Fused MFMA attention (head dim 64)
 // ---------------------------------------------------------------------------
 // seg: the int32 [b, s] run bounds of _attn_seg.seg_bounds (packed sequences), or none
+// d: the head dim of the kernel family, 64 or 128 (_attn_d128)
 AttnParams attn_params(const char* fn, const at::Tensor& qkv, const OptTensor& mask, double p_drop,
-                       int64_t seed, const OptTensor& seg) {
+                       int64_t seed, const OptTensor& seg, int d = 64) {
   check_nd(fn, "qkv", qkv, qkv, 5);
-  TORCH_CHECK(qkv.size(2) == 3 && qkv.size(4) == 64, fn, ": qkv must be [b, s, 3, h, 64]");
+  TORCH_CHECK(qkv.size(2) == 3 && qkv.size(4) == d, fn, ": qkv must be [b, s, 3, h, ", d, "]");
   AttnParams p{};
   p.qkv = qkv.data_ptr();
   p.b = (int)qkv.size(0);
   p.s = (int)qkv.size(1);
   p.h = (int)qkv.size(3);
-  p.scale_log2 = (float)(1.4426950408889634 / 8.0);
+  p.scale_log2 = (float)(1.4426950408889634 / (d == 64 ? 8.0 : std::sqrt((double)d)));
   p.mask = vec_ptr_opt(fn, "mask", mask, qkv, (int64_t)p.b * p.s);
   p.thresh = drop_thresh(fn, p_drop);
   p.p_drop = (float)p_drop;
@@ -109,6 +112,40 @@ std::vector<at::Tensor> attn_bwd(const char* fn, const at::Tensor& qkv, const at
       dqkv.data_ptr(), cur_stream(), want_bsum ? bsum.data_ptr<float>() : nullptr);
   if (want_bsum) return {dqkv, bsum};
   return {dqkv};
+}
+
+// Head dim 128 (mv_attn_d128.hip): qkv [b, s, 3, h, 128] -> (out [b, s, h, 128], lse [b, h, s])
+std::vector<at::Tensor> attn128_fwd(const at::Tensor& qkv, const OptTensor& mask, double p_drop,
+                                    int64_t seed, const OptTensor& seg, bool causal) {
+  const char* fn = "_attn_d128.fwd";
+  AttnParams p = attn_params(fn, qkv, mask, p_drop, seed, seg, 128);
+  TORCH_CHECK((int64_t)p.b * p.h <= 65535, fn, ": b*h must be <= 65535 (grid)");
+  c10::DeviceGuard guard(qkv.device());
+  at::Tensor out = at::empty({p.b, p.s, p.h, 128}, qkv.options());
+  at::Tensor lse = at::empty({p.b, p.h, p.s}, qkv.options().dtype(at::kFloat));
+  p.out = out.data_ptr();
+  p.lse = lse.data_ptr<float>();
+  mv_attn_d128_fwd(p, causal, cur_stream());
+  return {out, lse};
+}
+
+// -> dqkv; delta [b, h, s] fp32 is the only scratch (dq128_kernel accumulates dQ in registers)
+at::Tensor attn128_bwd(const at::Tensor& qkv, const at::Tensor& out, const at::Tensor& dout,
+                       const at::Tensor& lse, const OptTensor& mask, double p_drop, int64_t seed,
+                       const OptTensor& seg, bool causal) {
+  const char* fn = "_attn_d128.bwd";
+  AttnParams p = attn_params(fn, qkv, mask, p_drop, seed, seg, 128);
+  TORCH_CHECK((int64_t)p.b * p.h <= 65535, fn, ": b*h must be <= 65535 (grid)");
+  const int64_t bsh = (int64_t)p.b * p.s * p.h;
+  check_mn(fn, "out", out, qkv, bsh, 128);
+  check_mn(fn, "dout", dout, qkv, bsh, 128);
+  p.lse = vec_ptr(fn, "lse", lse, qkv, bsh);
+  c10::DeviceGuard guard(qkv.device());
+  at::Tensor delta = at::empty({bsh}, qkv.options().dtype(at::kFloat));
+  at::Tensor dqkv = at::empty_like(qkv);
+  mv_attn_d128_bwd(p, causal, out.data_ptr(), dout.data_ptr(), delta.data_ptr<float>(),
+                   dqkv.data_ptr(), cur_stream());
+  return dqkv;
 }
 
 at::Tensor attn_dropout_mask(int64_t b, int64_t h, int64_t s, double p_drop, int64_t seed,
@@ -488,4 +525,15 @@ void bind_bert(pybind11::module_& m) {
          pybind11::arg("qkv"), pybind11::arg("out"), pybind11::arg("dout"), pybind11::arg("lse"),
          pybind11::arg("mask"), pybind11::arg("p_drop"), pybind11::arg("seed"),
          pybind11::arg("seg") = pybind11::none());
+  // head dim 128, private for the same reason: one forward and one backward, the run bounds and
+  // causal as optional trailing operands
+  pybind11::module_ dg = m.def_submodule(
+      "_attn_d128", "fused MFMA attention at head dim 128: dense, packed runs, causal, or both");
+  dg.def("fwd", &attn128_fwd, "attention forward -> (out [b,s,h,128], lse)", pybind11::arg("qkv"),
+         pybind11::arg("mask"), pybind11::arg("p_drop"), pybind11::arg("seed"),
+         pybind11::arg("seg") = pybind11::none(), pybind11::arg("causal") = false);
+  dg.def("bwd", &attn128_bwd, "attention backward -> dqkv", pybind11::arg("qkv"),
+         pybind11::arg("out"), pybind11::arg("dout"), pybind11::arg("lse"), pybind11::arg("mask"),
+         pybind11::arg("p_drop"), pybind11::arg("seed"), pybind11::arg("seg") = pybind11::none(),
+         pybind11::arg("causal") = false);
 }

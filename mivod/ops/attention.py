@@ -6,6 +6,12 @@
 * GPU, bf16, head dim 64 -> the hand-written MFMA kernels in
   ``csrc/kernels/mv_attn.hip`` (fused QK^T / online softmax / dropout / PV
   forward; FlashAttention-2-style backward with deterministic dQ partials).
+* GPU, bf16, head dim 128 -> the kernels of ``csrc/kernels/mv_attn_d128.hip``
+  (docs/ATTENTION_D128.md): the same forward at twice the width, and a backward in two
+  kernels, a query-block owner that keeps dQ in registers over every key block and a
+  key-block owner for dK / dV, with no dQ partials.  Same mask contract, segments, ``causal``
+  and dropout hash as below; ``bias_slot`` is accepted and its ``partials`` stay ``None``
+  (the projection then sums the columns of dqkv itself).
 * anything else -> ``attention_math`` (batched GEMMs + fp32 softmax), which is
   also the numerics reference for the kernels.
 
@@ -104,7 +110,9 @@ class _FusedAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, mask, p_drop, seed, slot=None, seg=None, causal=False):
         nat = K.native()
-        if causal:
+        if qkv.shape[-1] == 128:
+            out, lse = nat._attn_d128.fwd(qkv, mask, float(p_drop), int(seed), seg, bool(causal))
+        elif causal:
             out, lse = nat._attn_causal.fwd(qkv, mask, float(p_drop), int(seed), seg)
         elif seg is None:
             out, lse = nat.attn_fwd(qkv, mask, float(p_drop), int(seed))
@@ -124,6 +132,8 @@ class _FusedAttention(torch.autograd.Function):
             dout = dout.to(torch.bfloat16)
         nat = K.native()
         args = (qkv, out, dout, lse, mask, ctx.p_drop, ctx.seed)
+        if qkv.shape[-1] == 128:        # no column sums: the slot's partials stay None
+            return nat._attn_d128.bwd(*args, seg, ctx.causal), None, None, None, None, None, None
         bsum = ctx.slot is not None and qkv.shape[1] <= 128
         if ctx.causal:
             res = (nat._attn_causal.bwd_bsum if bsum else nat._attn_causal.bwd)(*args, seg)
@@ -140,7 +150,7 @@ class _FusedAttention(torch.autograd.Function):
 
 def fused_available(qkv: torch.Tensor) -> bool:
     return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 5 and
-            qkv.shape[-1] == 64 and fusion.on("attention"))
+            qkv.shape[-1] in (64, 128) and fusion.on("attention"))
 
 
 def mask_to_key_bias(mask_bias, b, s):
