@@ -46,5 +46,13 @@ void mv_attn_causal_bwd(const AttnParams& p, const void* out, const void* dout, 
 void mv_attn_d128_fwd(const AttnParams& p, bool causal, hipStream_t st);
 void mv_attn_d128_bwd(const AttnParams& p, bool causal, const void* out, const void* dout,
                       float* delta, void* dqkv, hipStream_t st);
+// grouped-query attention at head dim 128 (the GQA forms of mv_attn_d128.hip,
+// docs/ATTENTION_GQA.md): p.qkv [b, s, p.h + 2 hkv, 128], a token's p.h query heads, then hkv
+// key heads, then hkv value heads; p.h % hkv == 0 and query head i reads KV head i / (p.h /
+// hkv).  out, lse, delta and the dropout hash are per query head as above; dqkv in qkv's
+// layout, dK / dV summed over each group in registers and stored once.
+void mv_attn_gqa_fwd(const AttnParams& p, int hkv, bool causal, hipStream_t st);
+void mv_attn_gqa_bwd(const AttnParams& p, int hkv, bool causal, const void* out, const void* dout,
+                     float* delta, void* dqkv, hipStream_t st);
 void mv_attn_dropout_mask(int b, int h, int s, uint32_t seed, uint32_t thresh, uint8_t* keep,
                           hipStream_t st);

@@ -19,6 +19,13 @@
 //                   queries through LDS, P and dP recomputed, dV^T += dO^T Z and
 //                   dK^T += Q^T dS in 8 + 8 accumulator tiles.  dS never touches LDS.
 //
+// GQA (docs/ATTENTION_GQA.md): the same three kernels over qkv [b, s, hq + 2 hkv, 128] (a token
+// holds the hq query heads, then the hkv key heads, then the hkv value heads; p.h = hq, query
+// head i reads KV head i / G, G = hq / hkv).  The query-block owners give a workgroup's 64 rows
+// to HW heads x 64 / HW tokens of one KV head (HW the largest of 4, 2, 1 dividing G), so a staged
+// K / V block serves HW heads; the key-block owner loops over the G heads of its KV head into
+// the same accumulators and stores dK / dV once.  With GQA = false all of it is compiled out.
+//
 // LDS images: [64][128 + LP] bf16, LP = 16: rows of 288 B.  The LDS has 64 banks of 4 B (256 B
 // per pass).  (a) The transposed read (tr8): one 32-lane half reads 8 consecutive rows
 // (groups g, g + 1: rows 4g .. 4g + 7), 32 B of each; row r starts at 288 r mod 256 = 32 r, so
@@ -96,14 +103,45 @@ __device__ __forceinline__ int query_block() {
   return CAUSAL ? gridDim.x - 1 - (blockIdx.x + blockIdx.y) % gridDim.x : blockIdx.x;
 }
 
-struct Heads {       // per-(b, h) base pointers into qkv
+struct Heads {       // per-(b, query head) base pointers into qkv
   const __bf16 *q, *k, *v;
   int64_t tok;
 };
-__device__ __forceinline__ Heads heads_of(const AttnParams& p, int bi, int hi) {
-  const int64_t tok = 3LL * p.h * HD;
-  const __bf16* q = ((const __bf16*)p.qkv) + (int64_t)bi * p.s * tok + (int64_t)hi * HD;
-  return Heads{q, q + (int64_t)p.h * HD, q + 2LL * p.h * HD, tok};
+// GQA: a token is hq query heads, hkv key heads, hkv value heads; query head hi reads KV head
+// hi / G
+template <bool GQA>
+__device__ __forceinline__ Heads heads_of(const AttnParams& p, int hkv, int bi, int hi) {
+  if constexpr (GQA) {
+    const int64_t tok = (int64_t)(p.h + 2 * hkv) * HD;
+    const __bf16* t = ((const __bf16*)p.qkv) + (int64_t)bi * p.s * tok;
+    const __bf16* k = t + (int64_t)(p.h + hi / (p.h / hkv)) * HD;
+    return Heads{t + (int64_t)hi * HD, k, k + (int64_t)hkv * HD, tok};
+  } else {
+    const int64_t tok = 3LL * p.h * HD;
+    const __bf16* q = ((const __bf16*)p.qkv) + (int64_t)bi * p.s * tok + (int64_t)hi * HD;
+    return Heads{q, q + (int64_t)p.h * HD, q + 2LL * p.h * HD, tok};
+  }
+}
+
+// The rows of a query-block owner's wave: batch row bi, query head hi, tokens q0 .. q0 + 15.
+// GQA: blockIdx.y = ((b, KV head), chunk of HW heads), blockIdx.x a tile of T = 64 / HW tokens;
+// wave w takes head w % HW of the chunk and the tile's tokens from 16 (w / HW).  The K / V
+// images a workgroup stages belong to its one KV head.  Under CAUSAL tile x costs
+// ceil((x + 1) T / 64) key blocks: counted down and rotated like the 64-token blocks.
+template <bool CAUSAL, bool GQA>
+__device__ __forceinline__ void wave_rows(const AttnParams& p, int hkv, int w, int& bi, int& hi,
+                                          int& q0) {
+  if constexpr (GQA) {
+    const int G = p.h / hkv, HW = G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1, nch = G / HW;
+    const int kv = blockIdx.y / nch, ch = blockIdx.y % nch;
+    const int ws = __builtin_amdgcn_readfirstlane(w);
+    bi = kv / hkv;
+    hi = __builtin_amdgcn_readfirstlane((kv % hkv) * G + ch * HW + ws % HW);
+    q0 = __builtin_amdgcn_readfirstlane(query_block<CAUSAL>() * (QB / HW) + 16 * (ws / HW));
+  } else {
+    bi = blockIdx.y / p.h, hi = blockIdx.y % p.h;
+    q0 = query_block<CAUSAL>() * QB + w * 16;
+  }
 }
 
 // the ranges of a query-block owner: qr the keys of the lane's query, wr of the wave's 16
@@ -123,13 +161,14 @@ __device__ __forceinline__ void query_ranges(const AttnParams& p, int bi, int q,
 }
 
 // ---------------------------------------------------------------- forward
-template <bool SEG, bool CAUSAL>
-__global__ __launch_bounds__(256) void fwd128_kernel(AttnParams p) {
+template <bool SEG, bool CAUSAL, bool GQA>
+__global__ __launch_bounds__(256) void fwd128_kernel(AttnParams p, int hkv) {
   constexpr bool M = SEG || CAUSAL;
-  const int bh = blockIdx.y, bi = bh / p.h, hi = bh % p.h;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, g = l >> 4, c = l & 15;
-  const int q0 = query_block<CAUSAL>() * QB + w * 16;
-  const Heads hd = heads_of(p, bi, hi);
+  int bi, hi, q0;
+  wave_rows<CAUSAL, GQA>(p, hkv, w, bi, hi, q0);
+  const int bh = GQA ? bi * p.h + hi : blockIdx.y;
+  const Heads hd = heads_of<GQA>(p, hkv, bi, hi);
   __shared__ __attribute__((aligned(16))) __bf16 Ks[KB][LS];
   __shared__ __attribute__((aligned(16))) __bf16 Vs[KB][LS];       // row-major; V^T via tr8
 
@@ -237,16 +276,18 @@ __global__ __launch_bounds__(256) void fwd128_kernel(AttnParams p) {
 }
 
 // ---------------------------------------------------------------- dQ (and delta)
-template <bool SEG, bool CAUSAL>
-__global__ __launch_bounds__(256) void dq128_kernel(AttnParams p, const __bf16* __restrict__ out,
+template <bool SEG, bool CAUSAL, bool GQA>
+__global__ __launch_bounds__(256) void dq128_kernel(AttnParams p, int hkv,
+                                                     const __bf16* __restrict__ out,
                                                      const __bf16* __restrict__ dout,
                                                      float* __restrict__ delta,
                                                      __bf16* __restrict__ dqkv) {
   constexpr bool M = SEG || CAUSAL;
-  const int bh = blockIdx.y, bi = bh / p.h, hi = bh % p.h;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, g = l >> 4, c = l & 15;
-  const int q0 = query_block<CAUSAL>() * QB + w * 16, qc = q0 + c;
-  const Heads hd = heads_of(p, bi, hi);
+  int bi, hi, q0;
+  wave_rows<CAUSAL, GQA>(p, hkv, w, bi, hi, q0);
+  const int bh = GQA ? bi * p.h + hi : blockIdx.y, qc = q0 + c;
+  const Heads hd = heads_of<GQA>(p, hkv, bi, hi);
   const int64_t otok = (int64_t)p.h * HD;
   const int64_t obase = (int64_t)bi * p.s * otok + (int64_t)hi * HD;
   __shared__ __attribute__((aligned(16))) __bf16 Ks[KB][LS];       // row-major; K^T via tr8
@@ -339,18 +380,27 @@ __global__ __launch_bounds__(256) void dq128_kernel(AttnParams p, const __bf16* 
 // ---------------------------------------------------------------- dK, dV
 // CAUSAL: key block kb runs the query blocks from its own to the end, so ascending kb is
 // heavy-first as it stands; rotated by (b, h) for the XCDs like bwd_kernel's.
-template <bool SEG, bool CAUSAL>
-__global__ __launch_bounds__(256) void dkdv128_kernel(AttnParams p, const __bf16* __restrict__ dout,
+// GQA: blockIdx.y = (b, KV head); the G query heads of the group run one after the other, in
+// ascending order, through the same images into the same accumulators (a fixed order: two runs
+// are bit-identical), and dK / dV are rounded and stored once.
+template <bool SEG, bool CAUSAL, bool GQA>
+__global__ __launch_bounds__(256) void dkdv128_kernel(AttnParams p, int hkv,
+                                                       const __bf16* __restrict__ dout,
                                                        const float* __restrict__ delta,
                                                        __bf16* __restrict__ dqkv) {
   constexpr bool M = SEG || CAUSAL;
-  const int bh = blockIdx.y, bi = bh / p.h, hi = bh % p.h;
+  const int G = GQA ? p.h / hkv : 1;       // query heads per KV head
+  const int bi = blockIdx.y / (GQA ? hkv : p.h);
+  const int h0 = GQA ? (blockIdx.y % hkv) * G : blockIdx.y % p.h;       // the first of them
   const int kb = CAUSAL ? (blockIdx.x + blockIdx.y) % gridDim.x : blockIdx.x;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, g = l >> 4, c = l & 15;
   const int keyc = kb * KB + w * 16 + c;
-  const Heads hd = heads_of(p, bi, hi);
+  const Heads hd = heads_of<GQA>(p, hkv, bi, h0);
   const int64_t otok = (int64_t)p.h * HD;
-  const __bf16* dOb = dout + (int64_t)bi * p.s * otok + (int64_t)hi * HD;
+  // of the head in hand: the only one, or (GQA) stepped at the end of the head loop
+  int bh = GQA ? bi * p.h + h0 : blockIdx.y;
+  const __bf16* Qb = hd.q;
+  const __bf16* dOb = dout + (int64_t)bi * p.s * otok + (int64_t)h0 * HD;
   __shared__ __attribute__((aligned(16))) __bf16 Qs[QB][LS];        // row-major; Q^T, dO^T via tr8
   __shared__ __attribute__((aligned(16))) __bf16 dOs[QB][LS];
   __shared__ float lse_s[QB], del_s[QB];
@@ -366,7 +416,7 @@ __global__ __launch_bounds__(256) void dkdv128_kernel(AttnParams p, const __bf16
     dKt[n] = f32x4v{0.f, 0.f, 0.f, 0.f};
   }
   const float inv_keep = p.p_drop > 0.f ? 1.f / (1.f - p.p_drop) : 1.f;
-  const uint32_t dkey = drop_key(p.seed, (uint32_t)bh);
+  uint32_t dkey = drop_key(p.seed, (uint32_t)bh);
   const float kbias = (p.mask && keyc < p.s) ? p.mask[(int64_t)bi * p.s + keyc] * LOG2E : 0.f;
   // kr = the queries of this lane's key, wr = of the wave's 16 keys, br = of the block's 64
   Range kr{0, p.s}, wr{0, p.s}, br{0, p.s};
@@ -378,64 +428,72 @@ __global__ __launch_bounds__(256) void dkdv128_kernel(AttnParams p, const __bf16
   }
   const int qb_beg = M ? min(br.lo, p.s) / QB * QB : 0, qb_end = M ? br.hi : p.s;
 
-  for (int qb0 = qb_beg; qb0 < qb_end; qb0 += QB) {
-    __syncthreads();
-    stage2(Qs, hd.q, hd.tok, dOs, dOb, otok, qb0, p.s);
-    if (threadIdx.x < QB) {
-      const int qq = qb0 + threadIdx.x;
-      // lse = -inf (a query with no key) is staged as +inf, like a query past s: P = 0
-      const float lv = qq < p.s ? p.lse[(int64_t)bh * p.s + qq] : INFINITY;
-      lse_s[threadIdx.x] = lv == -INFINITY ? INFINITY : lv;
-      del_s[threadIdx.x] = qq < p.s ? delta[(int64_t)bh * p.s + qq] : 0.f;
-    }
-    __syncthreads();
+  // the ranges above depend on tokens only: one set for every head of the group
+  int j = 0;
+  do {
+    for (int qb0 = qb_beg; qb0 < qb_end; qb0 += QB) {
+      __syncthreads();
+      stage2(Qs, Qb, hd.tok, dOs, dOb, otok, qb0, p.s);
+      if (threadIdx.x < QB) {
+        const int qq = qb0 + threadIdx.x;
+        // lse = -inf (a query with no key) is staged as +inf, like a query past s: P = 0
+        const float lv = qq < p.s ? p.lse[(int64_t)bh * p.s + qq] : INFINITY;
+        lse_s[threadIdx.x] = lv == -INFINITY ? INFINITY : lv;
+        del_s[threadIdx.x] = qq < p.s ? delta[(int64_t)bh * p.s + qq] : 0.f;
+      }
+      __syncthreads();
 #pragma unroll
-    for (int ch = 0; ch < 2; ++ch) {         // 32-query chunks
-      if (M && !wr.meets(qb0 + 32 * ch, 32)) continue;       // Z = dS = 0 on all 32 queries
-      float zc[2][4], dsc[2][4];
+      for (int ch = 0; ch < 2; ++ch) {         // 32-query chunks
+        if (M && !wr.meets(qb0 + 32 * ch, 32)) continue;       // Z = dS = 0 on all 32 queries
+        float zc[2][4], dsc[2][4];
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int qt = 2 * ch + u;
-        if (M && !wr.meets(qb0 + 16 * qt, 16)) {       // none of these queries sees the wave's keys
+        for (int u = 0; u < 2; ++u) {
+          const int qt = 2 * ch + u;
+          if (M && !wr.meets(qb0 + 16 * qt, 16)) {       // none of these queries sees the wave's keys
 #pragma unroll
-          for (int r = 0; r < 4; ++r) zc[u][r] = dsc[u][r] = 0.f;
-          continue;
-        }
-        // sacc[r] = S(query qb0 + 16 qt + 4 g + r, key keyc); pacc[r] = dZ of the same pair
-        const f32x4v sacc = dot_tile(Qs, qt, g, c, kf), pacc = dot_tile(dOs, qt, g, c, vf);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int ql = 16 * qt + 4 * g + r;
-          float pr = 0.f;
-          if (M ? kr.has(qb0 + ql) : keyc < p.s)
-            pr = exp2f(sacc[r] * p.scale_log2 + kbias - lse_s[ql]);
-          float z = pr, dzd = pacc[r];
-          if (p.p_drop > 0.f) {
-            const bool kp = keep_elem(dkey, (uint32_t)(qb0 + ql), (uint32_t)keyc, p.thresh);
-            z = kp ? pr * inv_keep : 0.f;
-            dzd = kp ? dzd * inv_keep : 0.f;
+            for (int r = 0; r < 4; ++r) zc[u][r] = dsc[u][r] = 0.f;
+            continue;
           }
-          zc[u][r] = z;
-          dsc[u][r] = pr * (dzd - del_s[ql]);
+          // sacc[r] = S(query qb0 + 16 qt + 4 g + r, key keyc); pacc[r] = dZ of the same pair
+          const f32x4v sacc = dot_tile(Qs, qt, g, c, kf), pacc = dot_tile(dOs, qt, g, c, vf);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int ql = 16 * qt + 4 * g + r;
+            float pr = 0.f;
+            if (M ? kr.has(qb0 + ql) : keyc < p.s)
+              pr = exp2f(sacc[r] * p.scale_log2 + kbias - lse_s[ql]);
+            float z = pr, dzd = pacc[r];
+            if (p.p_drop > 0.f) {
+              const bool kp = keep_elem(dkey, (uint32_t)(qb0 + ql), (uint32_t)keyc, p.thresh);
+              z = kp ? pr * inv_keep : 0.f;
+              dzd = kp ? dzd * inv_keep : 0.f;
+            }
+            zc[u][r] = z;
+            dsc[u][r] = pr * (dzd - del_s[ql]);
+          }
+        }
+        float zb[8] = {zc[0][0], zc[0][1], zc[0][2], zc[0][3], zc[1][0], zc[1][1], zc[1][2], zc[1][3]};
+        float sb[8] = {dsc[0][0], dsc[0][1], dsc[0][2], dsc[0][3],
+                       dsc[1][0], dsc[1][1], dsc[1][2], dsc[1][3]};
+        const bf16x8 zf = pack8(zb), sf = pack8(sb);
+        const int qa = 32 * ch + 4 * g, qbb = 32 * ch + 16 + 4 * g;
+#pragma unroll
+        for (int n = 0; n < NDT; ++n) {
+          dVt[n] = mfma(tr8(&dOs[0][0], LS, qa, qbb, 16 * n, c), zf, dVt[n]);
+          dKt[n] = mfma(tr8(&Qs[0][0], LS, qa, qbb, 16 * n, c), sf, dKt[n]);
         }
       }
-      float zb[8] = {zc[0][0], zc[0][1], zc[0][2], zc[0][3], zc[1][0], zc[1][1], zc[1][2], zc[1][3]};
-      float sb[8] = {dsc[0][0], dsc[0][1], dsc[0][2], dsc[0][3],
-                     dsc[1][0], dsc[1][1], dsc[1][2], dsc[1][3]};
-      const bf16x8 zf = pack8(zb), sf = pack8(sb);
-      const int qa = 32 * ch + 4 * g, qbb = 32 * ch + 16 + 4 * g;
-#pragma unroll
-      for (int n = 0; n < NDT; ++n) {
-        dVt[n] = mfma(tr8(&dOs[0][0], LS, qa, qbb, 16 * n, c), zf, dVt[n]);
-        dKt[n] = mfma(tr8(&Qs[0][0], LS, qa, qbb, 16 * n, c), sf, dKt[n]);
-      }
     }
-  }
+    if constexpr (GQA) {       // the next query head of the group
+      dkey = drop_key(p.seed, (uint32_t)++bh);
+      Qb += HD, dOb += HD;
+    }
+  } while (GQA && ++j < G);
   // dKt[n][r] = dK^T(dim 16 n + 4 g + r, key keyc): 4 consecutive dims, one 8-byte store
   if (keyc < p.s) {
     const float sc = p.scale_log2 / LOG2E;   // 1 / sqrt(128)
-    __bf16* dk = dqkv + ((int64_t)bi * p.s + keyc) * hd.tok + (int64_t)p.h * HD + (int64_t)hi * HD;
-    __bf16* dv = dk + (int64_t)p.h * HD;
+    __bf16* dk = dqkv + ((int64_t)bi * p.s + keyc) * hd.tok + (hd.k - hd.q) + (int64_t)h0 * HD;
+    __bf16* dv = dk + (hd.v - hd.k);
 #pragma unroll
     for (int n = 0; n < NDT; ++n) {
       *reinterpret_cast<u32x2*>(dk + 16 * n + 4 * g) =
@@ -446,34 +504,67 @@ __global__ __launch_bounds__(256) void dkdv128_kernel(AttnParams p, const __bf16
   }
 }
 
-template <bool SEG, bool CAUSAL>
-void launch_fwd(const AttnParams& p, hipStream_t st) {
+// hkv is read by the GQA forms only.  GQA: the query-block owners launch tiles of T = 64 / HW
+// tokens by (b, KV head, chunk of HW heads), the key-block owner 64-key blocks by (b, KV head)
+template <bool SEG, bool CAUSAL, bool GQA>
+void launch_fwd(const AttnParams& p, int hkv, hipStream_t st) {
   // CAUSAL: blockIdx.x counts the query blocks down, rotated by (b, h): heavy first
-  hipLaunchKernelGGL((fwd128_kernel<SEG, CAUSAL>), dim3((p.s + QB - 1) / QB, p.b * p.h), dim3(256), 0,
-                     st, p);
+  dim3 grid((p.s + QB - 1) / QB, p.b * p.h);
+  if constexpr (GQA) {
+    const int G = p.h / hkv, HW = G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1, T = QB / HW;
+    grid = dim3((p.s + T - 1) / T, p.b * hkv * (G / HW));
+  }
+  hipLaunchKernelGGL((fwd128_kernel<SEG, CAUSAL, GQA>), grid, dim3(256), 0, st, p, hkv);
 }
 
-template <bool SEG, bool CAUSAL>
-void launch_bwd(const AttnParams& p, const void* out, const void* dout, float* delta, void* dqkv,
-                hipStream_t st) {
-  const dim3 grid((p.s + QB - 1) / QB, p.b * p.h);       // QB == KB: one grid for both owners
-  hipLaunchKernelGGL((dq128_kernel<SEG, CAUSAL>), grid, dim3(256), 0, st, p, (const __bf16*)out,
-                     (const __bf16*)dout, delta, (__bf16*)dqkv);
-  hipLaunchKernelGGL((dkdv128_kernel<SEG, CAUSAL>), grid, dim3(256), 0, st, p, (const __bf16*)dout,
-                     (const float*)delta, (__bf16*)dqkv);
+template <bool SEG, bool CAUSAL, bool GQA>
+void launch_bwd(const AttnParams& p, int hkv, const void* out, const void* dout, float* delta,
+                void* dqkv, hipStream_t st) {
+  dim3 grid((p.s + QB - 1) / QB, p.b * p.h), kgrid = grid;       // QB == KB: one grid for both owners
+  if constexpr (GQA) {
+    const int G = p.h / hkv, HW = G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1, T = QB / HW;
+    grid = dim3((p.s + T - 1) / T, p.b * hkv * (G / HW));
+    kgrid = dim3((p.s + KB - 1) / KB, p.b * hkv);
+  }
+  hipLaunchKernelGGL((dq128_kernel<SEG, CAUSAL, GQA>), grid, dim3(256), 0, st, p, hkv,
+                     (const __bf16*)out, (const __bf16*)dout, delta, (__bf16*)dqkv);
+  hipLaunchKernelGGL((dkdv128_kernel<SEG, CAUSAL, GQA>), kgrid, dim3(256), 0, st, p, hkv,
+                     (const __bf16*)dout, (const float*)delta, (__bf16*)dqkv);
+}
+
+template <bool GQA>
+void fwd_form(const AttnParams& p, int hkv, bool causal, hipStream_t st) {
+  if (p.b * p.h == 0) return;
+  if (p.seg) (causal ? launch_fwd<true, true, GQA> : launch_fwd<true, false, GQA>)(p, hkv, st);
+  else (causal ? launch_fwd<false, true, GQA> : launch_fwd<false, false, GQA>)(p, hkv, st);
+}
+
+template <bool GQA>
+void bwd_form(const AttnParams& p, int hkv, bool causal, const void* out, const void* dout,
+              float* delta, void* dqkv, hipStream_t st) {
+  if (p.b * p.h == 0) return;
+  if (p.seg)
+    (causal ? launch_bwd<true, true, GQA> : launch_bwd<true, false, GQA>)(p, hkv, out, dout, delta, dqkv, st);
+  else
+    (causal ? launch_bwd<false, true, GQA> : launch_bwd<false, false, GQA>)(p, hkv, out, dout, delta, dqkv, st);
 }
 
 }  // namespace
 
 void mv_attn_d128_fwd(const AttnParams& p, bool causal, hipStream_t st) {
-  if (p.b * p.h == 0) return;
-  if (p.seg) (causal ? launch_fwd<true, true> : launch_fwd<true, false>)(p, st);
-  else (causal ? launch_fwd<false, true> : launch_fwd<false, false>)(p, st);
+  fwd_form<false>(p, p.h, causal, st);
 }
 
 void mv_attn_d128_bwd(const AttnParams& p, bool causal, const void* out, const void* dout,
                       float* delta, void* dqkv, hipStream_t st) {
-  if (p.b * p.h == 0) return;
-  if (p.seg) (causal ? launch_bwd<true, true> : launch_bwd<true, false>)(p, out, dout, delta, dqkv, st);
-  else (causal ? launch_bwd<false, true> : launch_bwd<false, false>)(p, out, dout, delta, dqkv, st);
+  bwd_form<false>(p, p.h, causal, out, dout, delta, dqkv, st);
+}
+
+void mv_attn_gqa_fwd(const AttnParams& p, int hkv, bool causal, hipStream_t st) {
+  fwd_form<true>(p, hkv, causal, st);
+}
+
+void mv_attn_gqa_bwd(const AttnParams& p, int hkv, bool causal, const void* out, const void* dout,
+                     float* delta, void* dqkv, hipStream_t st) {
+  bwd_form<true>(p, hkv, causal, out, dout, delta, dqkv, st);
 }

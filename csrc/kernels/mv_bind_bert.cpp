@@ -27,17 +27,12 @@ uint32_t drop_thresh(const char* fn, double p) {
 // ---------------------------------------------------------------------------
 // Fused MFMA attention (head dim 64)
 // ---------------------------------------------------------------------------
+// The operands every layout shares, once p.b, p.s and p.h are set from qkv.
 // seg: the int32 [b, s] run bounds of _attn_seg.seg_bounds (packed sequences), or none
-// d: the head dim of the kernel family, 64 or 128 (_attn_d128)
-AttnParams attn_params(const char* fn, const at::Tensor& qkv, const OptTensor& mask, double p_drop,
-                       int64_t seed, const OptTensor& seg, int d = 64) {
-  check_nd(fn, "qkv", qkv, qkv, 5);
-  TORCH_CHECK(qkv.size(2) == 3 && qkv.size(4) == d, fn, ": qkv must be [b, s, 3, h, ", d, "]");
-  AttnParams p{};
+// d: the head dim of the kernel family, 64 or 128 (_attn_d128, _attn_gqa)
+void attn_common(const char* fn, AttnParams& p, const at::Tensor& qkv, const OptTensor& mask,
+                 double p_drop, int64_t seed, const OptTensor& seg, int d) {
   p.qkv = qkv.data_ptr();
-  p.b = (int)qkv.size(0);
-  p.s = (int)qkv.size(1);
-  p.h = (int)qkv.size(3);
   p.scale_log2 = (float)(1.4426950408889634 / (d == 64 ? 8.0 : std::sqrt((double)d)));
   p.mask = vec_ptr_opt(fn, "mask", mask, qkv, (int64_t)p.b * p.s);
   p.thresh = drop_thresh(fn, p_drop);
@@ -51,6 +46,17 @@ AttnParams attn_params(const char* fn, const at::Tensor& qkv, const OptTensor& m
     p.seg = reinterpret_cast<const uint32_t*>(
         vec_ptr<int32_t>(fn, "seg", *seg, qkv, (int64_t)p.b * p.s));
   }
+}
+
+AttnParams attn_params(const char* fn, const at::Tensor& qkv, const OptTensor& mask, double p_drop,
+                       int64_t seed, const OptTensor& seg, int d = 64) {
+  check_nd(fn, "qkv", qkv, qkv, 5);
+  TORCH_CHECK(qkv.size(2) == 3 && qkv.size(4) == d, fn, ": qkv must be [b, s, 3, h, ", d, "]");
+  AttnParams p{};
+  p.b = (int)qkv.size(0);
+  p.s = (int)qkv.size(1);
+  p.h = (int)qkv.size(3);
+  attn_common(fn, p, qkv, mask, p_drop, seed, seg, d);
   return p;
 }
 
@@ -145,6 +151,58 @@ at::Tensor attn128_bwd(const at::Tensor& qkv, const at::Tensor& out, const at::T
   at::Tensor dqkv = at::empty_like(qkv);
   mv_attn_d128_bwd(p, causal, out.data_ptr(), dout.data_ptr(), delta.data_ptr<float>(),
                    dqkv.data_ptr(), cur_stream());
+  return dqkv;
+}
+
+// Grouped-query attention at head dim 128 (the GQA forms of mv_attn_d128.hip): qkv [b, s, H, 128]
+// with H = hq + 2 kv_heads (query heads, key heads, value heads); p.h = hq
+AttnParams attn_gqa_params(const char* fn, const at::Tensor& qkv, int64_t kv_heads,
+                           const OptTensor& mask, double p_drop, int64_t seed,
+                           const OptTensor& seg) {
+  check_nd(fn, "qkv", qkv, qkv, 4);
+  TORCH_CHECK(qkv.size(3) == 128, fn, ": qkv must be [b, s, hq + 2 kv_heads, 128]");
+  const int64_t H = qkv.size(2);
+  TORCH_CHECK(kv_heads >= 1 && H > 2 * kv_heads && (H - kv_heads) % kv_heads == 0, fn,
+              ": qkv's ", H, " heads must be hq + 2 kv_heads with hq a multiple of kv_heads = ",
+              kv_heads);
+  AttnParams p{};
+  p.b = (int)qkv.size(0);
+  p.s = (int)qkv.size(1);
+  p.h = (int)(H - 2 * kv_heads);
+  TORCH_CHECK((int64_t)p.b * p.h <= 65535, fn, ": b*hq must be <= 65535 (grid)");
+  attn_common(fn, p, qkv, mask, p_drop, seed, seg, 128);
+  return p;
+}
+
+// -> (out [b, s, hq, 128], lse [b, hq, s])
+std::vector<at::Tensor> attn_gqa_fwd(const at::Tensor& qkv, int64_t kv_heads, const OptTensor& mask,
+                                     double p_drop, int64_t seed, const OptTensor& seg, bool causal) {
+  const char* fn = "_attn_gqa.fwd";
+  AttnParams p = attn_gqa_params(fn, qkv, kv_heads, mask, p_drop, seed, seg);
+  c10::DeviceGuard guard(qkv.device());
+  at::Tensor out = at::empty({p.b, p.s, p.h, 128}, qkv.options());
+  at::Tensor lse = at::empty({p.b, p.h, p.s}, qkv.options().dtype(at::kFloat));
+  p.out = out.data_ptr();
+  p.lse = lse.data_ptr<float>();
+  mv_attn_gqa_fwd(p, (int)kv_heads, causal, cur_stream());
+  return {out, lse};
+}
+
+// -> dqkv in qkv's layout; delta [b, hq, s] fp32 is the only scratch
+at::Tensor attn_gqa_bwd(const at::Tensor& qkv, int64_t kv_heads, const at::Tensor& out,
+                        const at::Tensor& dout, const at::Tensor& lse, const OptTensor& mask,
+                        double p_drop, int64_t seed, const OptTensor& seg, bool causal) {
+  const char* fn = "_attn_gqa.bwd";
+  AttnParams p = attn_gqa_params(fn, qkv, kv_heads, mask, p_drop, seed, seg);
+  const int64_t bsh = (int64_t)p.b * p.s * p.h;
+  check_mn(fn, "out", out, qkv, bsh, 128);
+  check_mn(fn, "dout", dout, qkv, bsh, 128);
+  p.lse = vec_ptr(fn, "lse", lse, qkv, bsh);
+  c10::DeviceGuard guard(qkv.device());
+  at::Tensor delta = at::empty({bsh}, qkv.options().dtype(at::kFloat));
+  at::Tensor dqkv = at::empty_like(qkv);
+  mv_attn_gqa_bwd(p, (int)kv_heads, causal, out.data_ptr(), dout.data_ptr(), delta.data_ptr<float>(),
+                  dqkv.data_ptr(), cur_stream());
   return dqkv;
 }
 
@@ -536,4 +594,15 @@ void bind_bert(pybind11::module_& m) {
          pybind11::arg("out"), pybind11::arg("dout"), pybind11::arg("lse"), pybind11::arg("mask"),
          pybind11::arg("p_drop"), pybind11::arg("seed"), pybind11::arg("seg") = pybind11::none(),
          pybind11::arg("causal") = false);
+  // grouped-query attention at head dim 128, private for the same reason
+  pybind11::module_ gg = m.def_submodule(
+      "_attn_gqa", "fused MFMA grouped-query attention at head dim 128: kv_heads shared KV heads");
+  gg.def("fwd", &attn_gqa_fwd, "qkv [b,s,hq+2 kv_heads,128] -> (out [b,s,hq,128], lse [b,hq,s])",
+         pybind11::arg("qkv"), pybind11::arg("kv_heads"), pybind11::arg("mask"),
+         pybind11::arg("p_drop"), pybind11::arg("seed"), pybind11::arg("seg") = pybind11::none(),
+         pybind11::arg("causal") = false);
+  gg.def("bwd", &attn_gqa_bwd, "grouped attention backward -> dqkv", pybind11::arg("qkv"),
+         pybind11::arg("kv_heads"), pybind11::arg("out"), pybind11::arg("dout"), pybind11::arg("lse"),
+         pybind11::arg("mask"), pybind11::arg("p_drop"), pybind11::arg("seed"),
+         pybind11::arg("seg") = pybind11::none(), pybind11::arg("causal") = false);
 }

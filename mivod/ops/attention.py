@@ -54,6 +54,19 @@ all, with ``segment_bounds`` they take the same direction-free bounds and derive
 query and the queries of a key from them, and they skip the tiles above the diagonal
 (docs/CAUSAL_ATTENTION.md).  ``attention_math(..., causal=True)`` puts ``-inf`` above the
 diagonal and gives a query with no key 0.
+
+Grouped-query attention
+-----------------------
+``grouped_attention(qkv, kv_heads, ...)`` takes ``qkv [b, s, hq + 2 * kv_heads, d]`` — within a
+token the ``hq`` query heads, then the ``kv_heads`` key heads, then the ``kv_heads`` value heads,
+as one fused projection writes them — and returns ``[b, s, hq * d]``.  Query head ``i`` reads
+key / value head ``i // G``, ``G = hq // kv_heads``.  Everything above holds with "(b, h)" read
+as "(b, query head)", and the dropout hash is that of ``(seed, b_index * hq + query_head)`` over
+(query, key): the result EQUALS ``attention`` on the tensor whose K and V heads are each
+repeated G times (``repeat_interleave``), with the dK / dV of the G copies summed — the kernels
+(GPU, bf16, d = 128: the ``GQA`` forms in ``csrc/kernels/mv_attn_d128.hip``,
+docs/ATTENTION_GQA.md) read each shared head in place and do that sum in registers, rounding
+once.  Anything else runs ``grouped_attention_math``, which builds the repeated tensor.
 """
 from __future__ import annotations
 
@@ -148,6 +161,27 @@ class _FusedAttention(torch.autograd.Function):
         return dqkv, None, None, None, None, None, None
 
 
+class _FusedGroupedAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, kv_heads, mask, p_drop, seed, seg, causal):
+        out, lse = K.native()._attn_gqa.fwd(qkv, kv_heads, mask, float(p_drop), int(seed), seg,
+                                            bool(causal))
+        ctx.save_for_backward(qkv, out, lse, mask, seg)
+        ctx.kv_heads, ctx.p_drop, ctx.seed, ctx.causal = kv_heads, float(p_drop), int(seed), bool(causal)
+        b, s, h, d = out.shape
+        return out.view(b, s, h * d)
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, mask, seg = ctx.saved_tensors
+        dout = dout.contiguous().view(out.shape)
+        if dout.dtype != torch.bfloat16:
+            dout = dout.to(torch.bfloat16)
+        dqkv = K.native()._attn_gqa.bwd(qkv, ctx.kv_heads, out, dout, lse, mask, ctx.p_drop, ctx.seed,
+                                        seg, ctx.causal)
+        return dqkv, None, None, None, None, None, None
+
+
 def fused_available(qkv: torch.Tensor) -> bool:
     return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 5 and
             qkv.shape[-1] in (64, 128) and fusion.on("attention"))
@@ -211,3 +245,56 @@ def attention(qkv: torch.Tensor, mask_bias=None, p_drop: float = 0.0, seed=None,
     return attention_math(qkv, mask_bias, p_drop,
                           segment_ids=None if segment_bounds is None else segment_bounds.ids,
                           causal=causal)
+
+
+def _expand_groups(qkv: torch.Tensor, kv_heads: int) -> torch.Tensor:
+    """``[b, s, hq + 2 kv_heads, d]`` -> ``[b, s, 3, hq, d]`` with every K / V head repeated G
+    times (autograd sums the copies' gradients)."""
+    hq = qkv.shape[2] - 2 * kv_heads
+    q, k, v = qkv.split([hq, kv_heads, kv_heads], dim=2)
+    g = hq // kv_heads
+    return torch.stack([q, k.repeat_interleave(g, dim=2), v.repeat_interleave(g, dim=2)], dim=2)
+
+
+def grouped_attention_math(qkv: torch.Tensor, kv_heads: int, mask_bias=None, p_drop: float = 0.0,
+                           keep_mask=None, segment_ids=None, causal: bool = False) -> torch.Tensor:
+    """``attention_math`` on the expanded tensor: the fallback and the numerics reference of
+    ``grouped_attention``."""
+    return attention_math(_expand_groups(qkv, kv_heads), mask_bias, p_drop, keep_mask,
+                          segment_ids, causal)
+
+
+def grouped_attention(qkv: torch.Tensor, kv_heads: int, mask_bias=None, p_drop: float = 0.0,
+                      seed=None, segment_ids=None, segment_bounds: "SegmentBounds" = None,
+                      causal: bool = False) -> torch.Tensor:
+    """Grouped-query / multi-query attention on ``qkv [b, s, hq + 2 * kv_heads, d]`` ->
+    ``[b, s, hq * d]``, see the module docstring.  ``kv_heads == hq`` is ``attention`` on the
+    ``[b, s, 3, hq, d]`` view of the same memory."""
+    if qkv.dim() != 4 or kv_heads < 1 or qkv.shape[2] <= 2 * kv_heads:
+        raise ValueError("qkv must be [b, s, hq + 2 * kv_heads, d]")
+    b, s, d = qkv.shape[0], qkv.shape[1], qkv.shape[3]
+    hq = qkv.shape[2] - 2 * kv_heads
+    if hq % kv_heads != 0:
+        raise ValueError(f"{hq} query heads are no multiple of kv_heads = {kv_heads}")
+    if kv_heads == hq:
+        return attention(qkv.reshape(b, s, 3, hq, d), mask_bias, p_drop, seed,
+                         segment_ids=segment_ids, segment_bounds=segment_bounds, causal=causal)
+    if segment_ids is not None and segment_bounds is not None:
+        raise ValueError("pass segment_ids or segment_bounds, not both")
+    if segment_ids is not None:
+        segment_bounds = _prepare_segments(segment_ids)
+    if segment_bounds is not None and tuple(segment_bounds.ids.shape) != (b, s):
+        raise ValueError(f"segment ids must be [b, s] = [{b}, {s}]")
+    if qkv.is_cuda and qkv.dtype == torch.bfloat16 and d == 128 and fusion.on("attention"):
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0 else 0
+        seg = None
+        if segment_bounds is not None:
+            if segment_bounds.bounds is None:
+                raise RuntimeError("segment_bounds was prepared off the kernel path")
+            seg = segment_bounds.bounds
+        return _FusedGroupedAttention.apply(qkv.contiguous(), int(kv_heads),
+                                            mask_to_key_bias(mask_bias, b, s), p_drop, seed, seg, causal)
+    return grouped_attention_math(qkv, kv_heads, mask_bias, p_drop,
+                                  segment_ids=None if segment_bounds is None else segment_bounds.ids,
+                                  causal=causal)
