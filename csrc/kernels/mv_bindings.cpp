@@ -1,6 +1,6 @@
 // PyTorch bindings for the mivod gfx950 kernels (module mivod._mvk).  The entry points
-// live in one source per domain (mv_bind_optim / _bn / _bert / _gemm / _conv.cpp), each
-// exporting a bind_<domain>(module).  Every entry point validates its operands on the host
+// live in one source per domain (mv_bind_optim / _bn / _bert / _gemm / _conv / _decoder.cpp),
+// each exporting a bind_<domain>(module).  Every entry point validates its operands on the host
 // with the helpers of mv_checks.h before a launch: a kernel is never started on operands
 // that disagree with the grid it assumes.  All launches go to the caller's current HIP
 // stream.
@@ -14,6 +14,7 @@ void bind_bn(pybind11::module_& m);
 void bind_bert(pybind11::module_& m);
 void bind_gemm(pybind11::module_& m);
 void bind_conv(pybind11::module_& m);
+void bind_decoder(pybind11::module_& m);
 
 // A tensor over device memory mivod owns elsewhere (the mesh's IPC staging
 // slot): no copy, no deleter — the owner outlives every view by construction.
@@ -37,4 +38,5 @@ PYBIND11_MODULE(_mvk, m) {
   bind_bert(m);
   bind_gemm(m);
   bind_conv(m);
+  bind_decoder(m);
 }

@@ -1,1 +1,2 @@
 """mivod.models."""
+from .llama import LlamaConfig, LlamaDecoderLayer, LlamaForCausalLM, LlamaModel  # noqa: F401
