@@ -1,5 +1,5 @@
 // Fused MFMA attention launchers — head dim 64: mv_attn.hip, mv_attn_seg.hip,
-// mv_attn_causal.hip; head dim 128: mv_attn_d128.hip.
+// mv_attn_causal.hip; head dim 128: mv_attn_d128.hip, mv_attn_decode.hip (one token on a KV cache).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,5 +54,24 @@ void mv_attn_d128_bwd(const AttnParams& p, bool causal, const void* out, const v
 void mv_attn_gqa_fwd(const AttnParams& p, int hkv, bool causal, hipStream_t st);
 void mv_attn_gqa_bwd(const AttnParams& p, int hkv, bool causal, const void* out, const void* dout,
                      float* delta, void* dqkv, hipStream_t st);
+// one-token attention against a KV cache at head dim 128 (mv_attn_decode.hip,
+// docs/ATTENTION_DECODE.md): batch row i's hq query heads attend keys [0, lens[i]) of its cache,
+// query head j on KV head j / (hq / hkv); hq % hkv == 0, hq / hkv <= 16, b hkv <= 65535.  lens is
+// read on the device and clamped to [0, s_max]; lens[i] == 0 gives out = 0, lse = -inf.
+struct AttnDecodeParams {
+  const void* q;        // bf16 [b, hq, 128]
+  const void* kv;       // bf16 [b, s_max, 2 hkv, 128]: a token's key heads, then its value heads
+  const int* lens;      // [b]
+  void* out;            // bf16 [b, hq, 128]
+  float* lse;           // [b, hq], log2 domain
+  float* part;          // scratch fp32 [b, hq, splits, 130]: (m, l, o[128]) per split
+  int b, hq, hkv, s_max;
+  int splits;           // 1 .. MV_ATTN_DECODE_MAX_SPLITS workgroups along the keys
+  float scale_log2;     // log2(e) / sqrt(128)
+};
+constexpr int MV_ATTN_DECODE_MAX_SPLITS = 64;
+// the launcher's own choice of splits, from b hkv and s_max alone (no host sync on lens)
+int mv_attn_decode_splits(int b_hkv, int s_max);
+void mv_attn_decode(const AttnDecodeParams& p, hipStream_t st);
 void mv_attn_dropout_mask(int b, int h, int s, uint32_t seed, uint32_t thresh, uint8_t* keep,
                           hipStream_t st);

@@ -206,6 +206,47 @@ at::Tensor attn_gqa_bwd(const at::Tensor& qkv, int64_t kv_heads, const at::Tenso
   return dqkv;
 }
 
+// One-token attention against a KV cache (mv_attn_decode.hip): q [b, hq, 128], kv_cache
+// [b, S_max, 2 kv_heads, 128] (a token's key heads, then its value heads), lens int32 [b] ->
+// (out [b, hq, 128], lse [b, hq]).  lens[i] <= S_max is the caller's contract; the kernel clamps.
+// splits: workgroups along the keys, 0 = the launcher's choice from b kv_heads and S_max.
+std::vector<at::Tensor> attn_decode_fwd(const at::Tensor& q, const at::Tensor& kv_cache,
+                                        int64_t kv_heads, const at::Tensor& lens, int64_t splits) {
+  const char* fn = "_attn_decode.fwd";
+  check_nd(fn, "q", q, q, 3);
+  check_nd(fn, "kv_cache", kv_cache, q, 4);
+  TORCH_CHECK(q.size(2) == 128 && kv_cache.size(3) == 128, fn,
+              ": q must be [b, hq, 128] and kv_cache [b, S_max, 2 kv_heads, 128]");
+  const int64_t b = q.size(0), hq = q.size(1), s_max = kv_cache.size(1);
+  TORCH_CHECK(kv_cache.size(0) == b, fn, ": kv_cache must hold q's ", b, " batch rows, not ",
+              kv_cache.size(0));
+  TORCH_CHECK(kv_heads >= 1 && kv_cache.size(2) == 2 * kv_heads, fn, ": kv_cache's ",
+              kv_cache.size(2), " heads must be 2 kv_heads = ", 2 * kv_heads);
+  TORCH_CHECK(hq >= 1 && hq % kv_heads == 0, fn, ": q's ", hq,
+              " heads must be a multiple of kv_heads = ", kv_heads);
+  TORCH_CHECK(hq / kv_heads <= 16, fn, ": at most 16 query heads per KV head, not ", hq / kv_heads);
+  TORCH_CHECK(b * kv_heads <= 65535, fn, ": b*kv_heads must be <= 65535 (grid)");
+  TORCH_CHECK(s_max < (int64_t(1) << 30), fn, ": S_max must be < 2^30");
+  TORCH_CHECK(splits >= 0 && splits <= MV_ATTN_DECODE_MAX_SPLITS, fn, ": splits must be in [0, ",
+              MV_ATTN_DECODE_MAX_SPLITS, "]");
+  AttnDecodeParams p{};
+  p.lens = vec_ptr<int32_t>(fn, "lens", lens, q, b);
+  p.q = q.data_ptr();
+  p.kv = kv_cache.data_ptr();
+  p.b = (int)b, p.hq = (int)hq, p.hkv = (int)kv_heads, p.s_max = (int)s_max;
+  p.splits = splits ? (int)splits : mv_attn_decode_splits((int)(b * kv_heads), (int)s_max);
+  p.scale_log2 = (float)(1.4426950408889634 / std::sqrt(128.0));
+  c10::DeviceGuard guard(q.device());
+  at::Tensor out = at::empty({b, hq, 128}, q.options());
+  at::Tensor lse = at::empty({b, hq}, q.options().dtype(at::kFloat));
+  at::Tensor part = at::empty({b, hq, (int64_t)p.splits, 130}, q.options().dtype(at::kFloat));
+  p.out = out.data_ptr();
+  p.lse = lse.data_ptr<float>();
+  p.part = part.data_ptr<float>();
+  mv_attn_decode(p, cur_stream());
+  return {out, lse};
+}
+
 at::Tensor attn_dropout_mask(int64_t b, int64_t h, int64_t s, double p_drop, int64_t seed,
                              at::Device device) {
   c10::DeviceGuard guard(device);
@@ -605,4 +646,16 @@ void bind_bert(pybind11::module_& m) {
          pybind11::arg("kv_heads"), pybind11::arg("out"), pybind11::arg("dout"), pybind11::arg("lse"),
          pybind11::arg("mask"), pybind11::arg("p_drop"), pybind11::arg("seed"),
          pybind11::arg("seg") = pybind11::none(), pybind11::arg("causal") = false);
+  // one query token per batch row against a KV cache, private for the same reason
+  pybind11::module_ kg = m.def_submodule(
+      "_attn_decode", "split-KV grouped-query attention of one token over a KV cache, head dim 128");
+  kg.def("fwd", &attn_decode_fwd,
+         "q [b,hq,128], kv_cache [b,S_max,2 kv_heads,128], lens int32 [b] -> (out [b,hq,128], lse [b,hq])",
+         pybind11::arg("q"), pybind11::arg("kv_cache"), pybind11::arg("kv_heads"),
+         pybind11::arg("lens"), pybind11::arg("splits") = 0);
+  kg.def("splits", [](int64_t b_kv_heads, int64_t s_max) {
+           return mv_attn_decode_splits((int)b_kv_heads, (int)s_max);
+         },
+         "the split count fwd chooses for splits = 0", pybind11::arg("b_kv_heads"),
+         pybind11::arg("s_max"));
 }

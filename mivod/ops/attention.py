@@ -67,6 +67,21 @@ repeated G times (``repeat_interleave``), with the dK / dV of the G copies summe
 (GPU, bf16, d = 128: the ``GQA`` forms in ``csrc/kernels/mv_attn_d128.hip``,
 docs/ATTENTION_GQA.md) read each shared head in place and do that sum in registers, rounding
 once.  Anything else runs ``grouped_attention_math``, which builds the repeated tensor.
+
+Decoding
+--------
+``decode_attention(q, kv_cache, kv_heads, lens)`` is the attention of ONE new token per batch row
+against a cache: ``q [b, hq, d]`` are the token's rotated query heads, ``kv_cache
+[b, S_max, 2 * kv_heads, d]`` holds per cached token its ``kv_heads`` key heads, then its
+``kv_heads`` value heads — the tail ``qkv[:, :, hq:]`` of the grouped ``qkv`` row, so appending a
+token is one slice copy — and ``lens [b]`` (int32) says that batch row ``i`` attends keys
+``[0, lens[i])``; the new token's own K / V are appended first, so ``lens`` counts it.  The result
+is ``[b, hq * d]``.  No mask, no dropout, no segments, and no autograd: the op is meant for
+``torch.no_grad()`` and returns a tensor without a graph.  ``lens[i] == 0`` is a query without a
+key (``out = 0``); ``lens[i] <= S_max`` is the caller's contract, and nothing at or past
+``lens[i]`` in the cache is read.  GPU, bf16, d = 128 and ``hq / kv_heads <= 16`` run the split-KV
+kernels of ``csrc/kernels/mv_attn_decode.hip`` (docs/ATTENTION_DECODE.md), which read ``lens`` on
+the device; anything else runs ``decode_attention_math``.
 """
 from __future__ import annotations
 
@@ -298,3 +313,43 @@ def grouped_attention(qkv: torch.Tensor, kv_heads: int, mask_bias=None, p_drop: 
     return grouped_attention_math(qkv, kv_heads, mask_bias, p_drop,
                                   segment_ids=None if segment_bounds is None else segment_bounds.ids,
                                   causal=causal)
+
+
+def decode_attention_math(q: torch.Tensor, kv_cache: torch.Tensor, kv_heads: int,
+                          lens: torch.Tensor) -> torch.Tensor:
+    """The fallback and the numerics reference of ``decode_attention``, for any dtype and device:
+    a ``[b, S_max]`` key mask from ``lens``, batched GEMMs and a softmax (fp32 for 16-bit
+    inputs).  What the cache holds at or past ``lens`` has no influence here either."""
+    b, hq, d = q.shape
+    s_max = kv_cache.shape[1]
+    k, v = kv_cache.split([kv_heads, kv_heads], dim=2)                   # [b, S_max, hkv, d]
+    dead = torch.arange(s_max, device=q.device)[None, :] >= lens.reshape(b, 1)      # [b, S_max]
+    scores = torch.einsum("bhgd,bshd->bhgs", q.reshape(b, kv_heads, hq // kv_heads, d), k)
+    if scores.dtype in (torch.bfloat16, torch.float16):
+        scores = scores.float()
+    scores = (scores * (1.0 / math.sqrt(d))).masked_fill(dead[:, None, None], -math.inf)
+    p = torch.nan_to_num(torch.softmax(scores, dim=-1), nan=0.0)         # lens == 0: no key at all
+    ctx = torch.einsum("bhgs,bshd->bhgd", p.to(v.dtype), v.masked_fill(dead[:, :, None, None], 0))
+    return ctx.reshape(b, hq * d)
+
+
+def decode_attention(q: torch.Tensor, kv_cache: torch.Tensor, kv_heads: int,
+                     lens: torch.Tensor) -> torch.Tensor:
+    """One new token per batch row against a KV cache: ``q [b, hq, d]``, ``kv_cache
+    [b, S_max, 2 * kv_heads, d]``, ``lens [b]`` -> ``[b, hq * d]``, see "Decoding" in the module
+    docstring.  Inference only: no autograd, use it under ``torch.no_grad()``."""
+    if q.dim() != 3 or kv_cache.dim() != 4 or kv_heads < 1:
+        raise ValueError("q must be [b, hq, d] and kv_cache [b, S_max, 2 * kv_heads, d]")
+    b, hq, d = q.shape
+    if tuple(kv_cache.shape) != (b, kv_cache.shape[1], 2 * kv_heads, d):
+        raise ValueError(f"kv_cache must be [{b}, S_max, {2 * kv_heads}, {d}]")
+    if hq % kv_heads != 0:
+        raise ValueError(f"{hq} query heads are no multiple of kv_heads = {kv_heads}")
+    if tuple(lens.shape) != (b,):
+        raise ValueError(f"lens must be [b] = [{b}]")
+    if (q.is_cuda and q.dtype == torch.bfloat16 and kv_cache.dtype == torch.bfloat16 and d == 128
+            and hq // kv_heads <= 16 and fusion.on("attention")):
+        out, _ = K.native()._attn_decode.fwd(q.detach().contiguous(), kv_cache.detach().contiguous(),
+                                             int(kv_heads), lens.to(torch.int32).contiguous())
+        return out.view(b, hq * d)
+    return decode_attention_math(q.detach(), kv_cache.detach(), kv_heads, lens)
